@@ -16,6 +16,13 @@ pivot row panel, each rank routes the sources whose rows it owns, and the output
 exchanged point to point so that every rank ends with the whole table.
 --graph ba selects config C4 (50,000-vertex Barabasi-Albert, m=4; sparse batched
 Bellman-Ford with sources sharded across ranks + output row exchange).
+
+A plain run sets up, warms up, times --steps steps and prints the result line.  --full adds what
+is measured or checked beside the headline: the cold call (srg_create + first call), the
+device-entry time of the host-entry build, the RoutingInfo build times, the CPU baselines and
+the oracle rows.  --dump-outputs DIR writes the table the last timed step produced as
+DIR/latency_ns.npy (float64) and DIR/packet_loss.npy (float32), a fixed seeded sample of its rows
+when the whole would pass 48 MB; the inputs are seeded, so two builds can be compared row for row.
 """
 import argparse
 import json
@@ -132,6 +139,37 @@ def cpu_baselines(edges, target_s, desc, sources=256):
                      "extrapolated": True, "full_run_estimate_s": round(V / best + setup1, 1)}}
 
 
+DUMP_BUDGET = 48 << 20  # --dump-outputs: bytes written in all (float32 / float64 .npy files)
+DUMP_SEED = 20240
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: what the timed path left in the caller's arrays after its last step, as
+    DIR/<name>.npy.  Integers go out as float64 (exact below 2^53), floats as float32.  Past
+    DUMP_BUDGET bytes in all, every array is cut to a fixed seeded sample of its first axis (the
+    same rows of arrays of the same length, the same from run to run).  arrays: name -> numpy
+    array or torch tensor; returns what was written, for the result line."""
+    import numpy as np
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    width = {k: (4 if str(a.dtype).endswith("float32") else 8) for k, a in arrays.items()}
+    total = sum(int(np.prod(a.shape)) * width[k] for k, a in arrays.items())
+    frac = min(1.0, DUMP_BUDGET / max(total, 1))
+    written = {}
+    for k, a in arrays.items():
+        n = int(a.shape[0])
+        take = n if frac >= 1.0 else max(1, int(n * frac))
+        if take < n:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=take, replace=False))
+            a = a[torch.as_tensor(idx, device=a.device)] if isinstance(a, torch.Tensor) else a[idx]
+        if isinstance(a, torch.Tensor):
+            a = a.cpu().numpy()
+        a = np.ascontiguousarray(a, dtype=np.float32 if width[k] == 4 else np.float64)
+        np.save(os.path.join(dirname, k + ".npy"), a)
+        written[k] = {"shape": list(a.shape), "dtype": str(a.dtype), "sampled_of": n if take < n else None}
+    return written
+
+
 def load_traffic(kernel_substr, workload_key):
     """HBM bytes per launch of the dominant kernel from the committed rocprofv3 PMC summary
     (profiles/fw_pmc_latest.json for the FW tile, profiles/sparse_pmc_latest.json for k_sparse_bf),
@@ -158,7 +196,9 @@ def bench_events(args, n=10**7, hosts=10000):
     from shadow_amd import events as ev
     dev = torch.device("cuda", 0)
     b, round_end = ev.synthetic_round(n, hosts, hosts, seed=7)
-    table = torch.randint(1_000_000, 100_000_000, (hosts, hosts), dtype=torch.int64, device=dev)
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(7)  # the same table from run to run
+    table = torch.randint(1_000_000, 100_000_000, (hosts, hosts), dtype=torch.int64, device=dev, generator=gen)
     db = ev.DeviceEventBatch(b, hosts, round_end, dev)
     deliver = torch.empty(n, dtype=torch.int64, device=dev)
     order = torch.empty(n, dtype=torch.int32, device=dev)
@@ -173,6 +213,9 @@ def bench_events(args, n=10**7, hosts=10000):
     torch.cuda.synchronize(dev)
     el = time.perf_counter() - t0
     ms = el * 1e3 / args.steps
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, {"deliver_time_ns": deliver, "queue_order": order, "host_offsets": off})
     cpu = None
     if not args.no_cpu:
         import oracle
@@ -198,7 +241,7 @@ def bench_events(args, n=10**7, hosts=10000):
                                    "peak": 8000.0, "unit": "GB/s",
                                    "frac": round(per_ev * n / (ms * 1e-3) / 1e9 / 8000.0, 4), "traffic": None,
                                    "bytes_per_event": per_ev, "note": "whole-call time, all kernels"},
-                      "cpu_baseline": cpu}), flush=True)
+                      "cpu_baseline": cpu, **({"dumped_outputs": dumped} if dumped else {})}), flush=True)
 
 
 def init_strong_router(local, dev):
@@ -495,8 +538,12 @@ def bench_multi(args):
     if not ok:
         log(f"[multi{G}] multi-device build refused by the gate ({reason}): running {G} independent replicas")
         return bench_replicas_inproc(args, G, edges, gdesc, seed, reason)
-    router, cold_ms = cold_call(lambda: MultiRouter(list(range(G))), args, edges, V)
-    log(f"[multi{G}] cold call (srg_multi_create + first call, unfaulted outputs): {cold_ms:.1f} ms")
+    if args.full:
+        router, cold_ms = cold_call(lambda: MultiRouter(list(range(G))), args, edges, V)
+        log(f"[multi{G}] cold call (srg_multi_create + first call, unfaulted outputs): {cold_ms:.1f} ms")
+    else:
+        router, cold_ms = MultiRouter(list(range(G))), None
+        apply_options(router, args)
     h_nodes = np.arange(V, dtype=np.uint32)
     h_lat = np.zeros((V, V), dtype=np.uint64)
     h_loss = np.zeros((V, V), dtype=np.float32)
@@ -523,14 +570,15 @@ def bench_multi(args):
     elapsed = time.perf_counter() - t0
     ms = elapsed * 1e3 / args.steps
     kind = s["path_kind"]
+    dumped = dump_outputs(args.dump_outputs, {"latency_ns": h_lat, "packet_loss": h_loss}) if args.dump_outputs else None
     ver = verify_rows(edges, h_lat, h_loss, V) if not args.no_verify else None
     roof = roofline_for(agg, kind, args, edges, V, workload_key(args, V, seed, G), kind == 0
                         and args.fw_symmetric != 0 and not edges.directed)
     emit(args, V, gdesc, edges, kind, G, G and V * args.steps / elapsed, ms, agg, s, roof, None,
          {"parallelism": f"multi{G} (one process, srg_multi: in-process group, pull collectives over xGMI)",
           "output": "full table in one host array (each GPU writes its sources' rows over its own PCIe link)",
-          "cold_call_ms": round(cold_ms, 1)},
-         {"verified_rows": ver}, steps_ms=step_stats(ts))
+          "cold_call_ms": round(cold_ms, 1) if cold_ms is not None else None},
+         {"verified_rows": ver, **({"dumped_outputs": dumped} if dumped else {})}, steps_ms=step_stats(ts))
 
 
 def multi_gate(G, args):
@@ -596,12 +644,14 @@ def bench_replicas_inproc(args, G, edges, gdesc, seed, reason):
     elapsed = time.perf_counter() - t0
     ms = elapsed * 1e3 / args.steps
     kind = s["path_kind"]
+    dumped = (dump_outputs(args.dump_outputs, {"latency_ns": tabs[0][0], "packet_loss": tabs[0][1]})
+              if args.dump_outputs else None)
     ver = verify_rows(edges, tabs[0][0], tabs[0][1], V) if not args.no_verify else None
     roof = roofline_for(agg, kind, args, edges, V, workload_key(args, V, seed, 1), kind == 0
                         and args.fw_symmetric != 0 and not edges.directed)
     emit(args, V, gdesc, edges, kind, G, G * V * args.steps / elapsed, ms, agg, s, roof, None,
          {"parallelism": f"replicas{G} (one process, one full build per GPU per step)", "fallback": reason},
-         {"verified_rows": ver}, scaling="weak", steps_ms=step_stats(ts))
+         {"verified_rows": ver, **({"dumped_outputs": dumped} if dumped else {})}, scaling="weak", steps_ms=step_stats(ts))
     for r in routers:
         r.close()
 
@@ -632,6 +682,14 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: the cold call, the device-entry time of the "
+                         "host-entry build, the RoutingInfo build times, the CPU baselines and the oracle rows "
+                         "(--no-cpu / --no-ri / --no-verify then drop single ones); without it a run sets up, "
+                         "warms up, times the steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step left in the caller's arrays as "
+                         "DIR/<name>.npy (float32 / float64; a fixed seeded sample of rows past 48 MB in all)")
     ap.add_argument("--vertices", type=int, default=10000)
     ap.add_argument("--seed", type=int, default=None)
     ap.add_argument("--lat-scale", type=int, default=1,
@@ -682,6 +740,8 @@ def main():
                     help="TIMING AID 'G:r': run rank r's share of a G-rank build alone, collectives elided "
                          "(outputs invalid; prints a diagnostic line, never the bench result)")
     args = ap.parse_args()
+    if not args.full:
+        args.no_cpu = args.no_verify = args.no_ri = True
     if args.config:
         args.graph, args.vertices = {"c1": ("complete", 1000), "c2": ("atlas", 4096), "c3": ("atlas", 10000),
                                      "c4": ("ba", 50000), "c5": ("events", 10000)}[args.config]
@@ -735,7 +795,7 @@ def main():
                 # RCCL row exchange so that every rank's own array holds the whole table
                 router.set_option(N.SRG_OPT_GATHER_OUTPUT, 0)
     if not strong:
-        if args.entry == "host" and not args.simulate_rank:
+        if args.full and args.entry == "host" and not args.simulate_rank:
             router, cold_ms = cold_call(lambda: Router(local), args, edges, V)
             log(f"[rank {rank}] cold call (srg_create + first call, unfaulted outputs): {cold_ms:.1f} ms")
         else:
@@ -746,7 +806,9 @@ def main():
         router.set_option(N.SRG_OPT_SIMULATE_RANK, sg * 1000 + sr)
         if not args.gather:  # as the N > 1 default: this rank's rows only
             router.set_option(N.SRG_OPT_GATHER_OUTPUT, 0)
-    dg = DeviceGraph(edges, dev)
+    # the edge list resident in HBM: the device entry's input (--full times it beside the host entry too)
+    want_dev_ms = args.full and args.entry == "host" and world == 1 and not args.simulate_rank
+    dg = DeviceGraph(edges, dev) if args.entry != "host" or want_dev_ms else None
     nodes = torch.arange(V, dtype=torch.int32, device=dev)
     shm = None
     if args.entry == "host":
@@ -804,10 +866,16 @@ def main():
     value = (1 if strong else world) * V * args.steps / elapsed
 
     kind = s["path_kind"]
+    dumped = None
+    if args.dump_outputs and not args.simulate_rank and (rank == 0 or args.entry != "host"):
+        # (N > 1: rank 0's host table is the whole table; device tables are per rank)
+        where = args.dump_outputs if world == 1 or args.entry == "host" else os.path.join(args.dump_outputs, f"rank{rank}")
+        dumped = dump_outputs(where, {"latency_ns": h_lat, "packet_loss": h_loss} if args.entry == "host" else
+                              {"latency_ns": out_lat, "packet_loss": out_loss})
     # the device-resident time of the same build (inputs and outputs in HBM): the kernel pipeline
     # alone, reported beside the host-entry headline
     dev_ms = None
-    if args.entry == "host" and world == 1 and not args.simulate_rank:
+    if want_dev_ms:
         ol = torch.empty((V, V), dtype=torch.int64, device=dev)
         os_ = torch.empty((V, V), dtype=torch.float32, device=dev)
         torch.cuda.synchronize(dev)
@@ -863,7 +931,7 @@ def main():
                 extra_cfg["cold_call_breakdown_ms"] = dict(COLD_BREAKDOWN)
         emit(args, V, gdesc, edges, kind, world, value, ms_per_step, agg, s, roofline, cpu, extra_cfg,
              {"device_entry_ms": round(dev_ms, 3) if dev_ms is not None else None, "verified_rows": ver,
-              "routing_info": ri_times}, steps_ms=step_stats(ts))
+              "routing_info": ri_times, **({"dumped_outputs": dumped} if dumped else {})}, steps_ms=step_stats(ts))
     if world > 1:
         dist.barrier()
         if shm is not None and rank == 0:

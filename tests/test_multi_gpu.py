@@ -238,9 +238,15 @@ def c3_single():
     the bench times it (edge list in host memory, FW beside the H2D, 1.2 GB table back): the
     reference table of the multi-rank tests, pinned to the oracle by test_c3_host_entry_oracle_rows."""
     e = synth.atlas_like(10000, seed=10000)
-    r = Router(0)
-    t = r.compute_shortest_paths(e, list(range(10000)))
-    r.close()
+    # (the codec's host-slow switch ships the rest of the list plain when the host narrows the chunks
+    # slower than the link would carry them -- a busy shared host on a router's first call -- and the
+    # overlap then falls back by design; this table must come from the overlapped build whatever the
+    # host's load, so the switch is held off as in test_fw_overlap.py)
+    with pytest.MonkeyPatch.context() as mp:
+        mp.setenv("SRG_CODEC_SLOW_AFTER", "1000000")
+        r = Router(0)
+        t = r.compute_shortest_paths(e, list(range(10000)))
+        r.close()
     assert t.stats["path_kind"] == N.SRG_PATH_DENSE_U32
     return e, t
 

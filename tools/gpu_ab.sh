@@ -15,7 +15,7 @@ tail -1 $O/pytest_gpu.log
 for i in $(seq 1 ${REPS:-3}); do
   for v in "$@"; do
     IFS='|' read -r name envs flags <<< "$v"
-    timeout -k 10 200 env $envs python -u bench.py --steps 10 --no-cpu --no-ri $flags > $O/${name}_$i.json 2> $O/${name}_$i.err || { tail -10 $O/${name}_$i.err; exit 1; }
+    timeout -k 10 200 env $envs python -u bench.py --full --steps 10 --no-cpu --no-ri $flags > $O/${name}_$i.json 2> $O/${name}_$i.err || { tail -10 $O/${name}_$i.err; exit 1; }
     python3 -c "import json; d=json.loads(open('$O/${name}_$i.json').read().strip().splitlines()[-1]); b=d['breakdown_ms']; print('$name', d['ms_per_step'], {k: round(x, 2) for k, x in b.items() if x})"
   done
 done
