@@ -4,6 +4,7 @@ hipcc compiles the HIP kernels + C ABI (routing.hip) and the host-side GML inges
 (gml.cpp) into one shared object with a plain C ABI (include/shadow_routing.h).
 -ffp-contract=off: Rust never contracts `1 - x*y` (mod.rs:328) into an FMA, so neither may we.
 """
+import glob
 import os
 import subprocess
 import sys
@@ -17,7 +18,9 @@ LIB = os.path.join(HERE, "libshadow_routing.so")
 LIB_TEST = os.path.join(HERE, "libshadow_routing_testhooks.so")
 SOURCES = [os.path.join(CSRC, "routing.hip"), os.path.join(CSRC, "gml.cpp"), os.path.join(CSRC, "comm.hip"),
            os.path.join(CSRC, "routing_info.cpp")]
-DEPS = SOURCES + [os.path.join(CSRC, "kernels.hip.h"), os.path.join(CSRC, "tight_sparse.hip.h"), os.path.join(CSRC, "comm.h"), os.path.join(CSRC, "sparse.hip.h"), os.path.join(CSRC, "sparse_ds.hip.h"), os.path.join(CSRC, "events.hip.h"), os.path.join(CSRC, "edge_codec.h"), os.path.join(CSRC, "xchg.hip.h"), os.path.join(CSRC, "internal.h"), os.path.join(CSRC, "guards.h"), os.path.join(ROOT, "include", "shadow_routing.h")]
+# every header under csrc/ (routing.hip is one translation unit over most of them): globbed, so a
+# new header cannot be left out of needs_build()
+DEPS = SOURCES + sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(ROOT, "include", "shadow_routing.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("SRG_OFFLOAD_ARCH", "gfx950")
 

@@ -917,7 +917,7 @@ __global__ void __launch_bounds__(256, 3) fw_bulk_lb(K* __restrict__ D, size_t l
                                                      int x0, int x1, LineMap lm, const int* __restrict__ tiles,
                                                      int maxI) {
     const int t = tiles[blockIdx.x];
-    if (t < 0) return;  // (a slot past a short XCD run, routing.hip xcd_tile_order)
+    if (t < 0) return;  // (a slot past a short XCD run, plan.h xcd_tile_order)
     int I, J;
     tri_tile(lm.nb, t, I, J);
     if (I == x0 || I == x1 || J == x0 || J == x1 || I > maxI) return;  // whole workgroup

@@ -1,15 +1,20 @@
-// routing.hip — MI355X routing-table builder: device pipeline + C ABI (include/shadow_routing.h).
+// routing.hip -- MI355X routing-table builder: device pipeline + C ABI (include/shadow_routing.h).
 //
 // Replaces NetworkGraph::compute_shortest_paths (src/main/network/graph/mod.rs:183-228) and
-// NetworkGraph::get_direct_paths (mod.rs:230-252) with a dense device pipeline:
-//   1. k_edge_scan       validate endpoints, count self-loops per vertex, record the raw
-//                        self-loop weight (diagonal, mod.rs:210-217), max edge latency
-//   2. k_w_lat/k_w_loss  dense W = lexicographic min over parallel edges (mod.rs:305-313)
-//   3. fw_phase1/fw_product   blocked min-plus Floyd-Warshall on latency (exact u32-sat or u64)
-//   4. tight_scan        per used source, the tight predecessors of every vertex
-//   5. k_loss_round      left-fold loss over the tight DAG, Jacobi rounds to a fixpoint
-//                        == petgraph Dijkstra's lexicographic (latency, loss) scores
-//   6. k_extract         used x used outputs, diagonal <- raw self-loop, unreachable check
+// NetworkGraph::get_direct_paths (mod.rs:230-252).  compute_device chooses the build:
+//   dense (run_dense)    k_edge_scan / k_lat_gcd validate; k_w_key + k_w_split build W; blocked
+//                        min-plus Floyd-Warshall (symmetric over line buffers when undirected);
+//                        k_certify, k_extract; then k_ess_mask -> tight_v5 -> k_loss_rows, or
+//                        tight_scan -> k_loss_round above the sparse-scan threshold
+//   sparse (run_sparse)  batched delta-stepping + loss fold (k_sparse_ds), or the lexicographic
+//                        Bellman-Ford sweeps (k_sparse_bf) for u64 labels
+// Files: env_switches.h (every SRG_* environment switch), host_pool.h (host worker pool), plan.h
+// (rank / XCD / scan-group splits) -- all three without HIP; dense.hip.h (run_dense) and
+// sparse_run.hip.h (run_sparse, choose_sparse), sections of this translation unit; the device
+// headers (kernels, tight_sparse, sparse, sparse_ds, events, xchg).  Still here, in order: the
+// validation / W / certify / extract kernels, the context (srg_ctx), prelude(), HostSink, the FW
+// schedules (stream_hop, fw_blocked, SymFw, FwOverlap), compute_device, direct paths, packet
+// events, the H2D codec, host_entry, extern "C".
 // No CPU fallback: every entry point fails loudly (status code) when HIP is unavailable.
 #include <hip/hip_runtime.h>
 #include <hsa/hsa.h>
@@ -37,6 +42,9 @@
 
 #include "../../include/shadow_routing.h"
 #include "internal.h"
+#include "env_switches.h"
+#include "host_pool.h"
+#include "plan.h"
 #include "kernels.hip.h"
 #include "guards.h"
 #include "edge_codec.h"
@@ -74,10 +82,14 @@ void set_err(char* buf, size_t len, const std::string& m) {
     if (buf && len) std::snprintf(buf, len, "%s", m.c_str());
 }
 
-// grow-only device buffer
+// grow-only device buffer; owns its allocation
 struct DevBuf {
     void* p = nullptr;
     size_t bytes = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { release(); }
     void* get(size_t need) {
         if (need <= bytes) return p;
         if (p) HIP_CHECK(hipFree(p));
@@ -92,6 +104,25 @@ struct DevBuf {
         p = nullptr;
         bytes = 0;
     }
+};
+
+// an owned hipEvent_t: null until created, destroyed with its owner
+struct Event {
+    hipEvent_t e = nullptr;
+    Event() = default;
+    Event(const Event&) = delete;
+    Event& operator=(const Event&) = delete;
+    Event(Event&& o) noexcept : e(o.e) { o.e = nullptr; }  // (vectors of events grow)
+    ~Event() {
+        if (e) (void)hipEventDestroy(e);
+    }
+    void create() {  // ordering only (no timestamps); a second call keeps the first event
+        if (!e) HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    }
+    void create_timed() {
+        if (!e) HIP_CHECK(hipEventCreate(&e));
+    }
+    operator hipEvent_t() const { return e; }
 };
 
 struct EdgeStats {
@@ -641,60 +672,6 @@ double ms_since(std::chrono::steady_clock::time_point t0) {
 
 }  // namespace
 
-// Host-side worker pool for the host entry's H2D codec: run(f) calls f(w, nw) on nw threads
-// (the caller is worker 0) and returns when all are done.
-struct HostPool {
-    std::vector<std::thread> th;
-    std::mutex run_mu;  // one job at a time: job / pending / gen are shared (callers on several threads queue)
-    std::mutex mu;
-    std::condition_variable cv, done_cv;
-    std::function<void(int, int)> job;
-    uint64_t gen = 0;
-    int pending = 0;
-    bool stop = false;
-    int size() const { return (int)th.size() + 1; }
-    void start(int n) {
-        for (int w = 1; w < n; ++w)
-            th.emplace_back([this, w] {
-                uint64_t seen = 0;
-                for (;;) {
-                    std::function<void(int, int)> f;
-                    {
-                        std::unique_lock<std::mutex> lk(mu);
-                        cv.wait(lk, [&] { return stop || gen != seen; });
-                        if (stop) return;
-                        seen = gen;
-                        f = job;
-                    }
-                    f(w, size());
-                    std::lock_guard<std::mutex> lk(mu);
-                    if (--pending == 0) done_cv.notify_one();
-                }
-            });
-    }
-    void run(const std::function<void(int, int)>& f) {
-        std::lock_guard<std::mutex> serial(run_mu);
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            job = f;
-            pending = (int)th.size();
-            ++gen;
-        }
-        cv.notify_all();
-        f(0, size());
-        std::unique_lock<std::mutex> lk(mu);
-        done_cv.wait(lk, [&] { return pending == 0; });
-    }
-    ~HostPool() {
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            stop = true;
-        }
-        cv.notify_all();
-        for (auto& t : th) t.join();
-    }
-};
-
 // The HSA agents of a HIP device (matched by PCI domain / bus / device), for SDMA copies.
 struct SdmaAgents {
     bool ok = false;
@@ -806,7 +783,7 @@ struct srg_ctx {
     HostPool* pool = nullptr;        // its host workers
     void* h_ring = nullptr;          // its page-locked staging ring (hipHostMalloc)
     size_t h_ring_bytes = 0;
-    hipEvent_t ev_ring[3] = {nullptr, nullptr, nullptr};
+    Event ev_ring[3];
     DevBuf b_n16s, b_n16d, b_n32l;   // narrowed edge arrays on the device
     DevBuf b_exc;                    // sequential-pair codec: a chunk's exceptions (index, src, dst)
     std::vector<std::vector<uint32_t>> codec_ex;  // its per-worker exception lists
@@ -815,9 +792,9 @@ struct srg_ctx {
     size_t own_row0 = 0, own_row1 = ~(size_t)0;  // the output rows this rank routed (multi-rank: [p0, p1))
     int late_loss = 1;               // host entry: edge losses shipped beside FW (SRG_OPT_LATE_LOSS)
     hipStream_t loss_stream = nullptr;  // = d2h_stream (see srg_create)
-    hipEvent_t ev_ledges = nullptr, ev_lin = nullptr, ev_ldone = nullptr, ev_wlate = nullptr;
+    Event ev_ledges, ev_lin, ev_ldone, ev_wlate;
     void* h_lring = nullptr;         // pinned ring of the late loss H2D
-    hipEvent_t ev_lring[3] = {nullptr, nullptr, nullptr};
+    Event ev_lring[3];
     int edge_shard = -1;             // host entry, multi-rank: ship 1/N of the edges, allgatherv the rest (SRG_OPT_EDGE_SHARD)
     const uint32_t* sim_edges = nullptr;  // simulated rank: the edge list whose other slices are resident
     size_t sim_E = 0;
@@ -828,19 +805,19 @@ struct srg_ctx {
     // host entry then waits for that registration (returns the arrays' device views, false if it
     // failed) instead of registering them itself
     std::function<bool(void** views, double* ms)> ext_reg;
-    std::vector<hipEvent_t> prof_events;
+    std::vector<Event> prof_events;  // timed pairs around the profiled launches (SRG_OPT_PROFILING)
     hipStream_t stream = nullptr;
     hipStream_t aux_stream = nullptr;   // FW lookahead: phase 1/2 of the next pivot block
     hipStream_t comm_stream = nullptr;  // pivot-panel broadcasts (multi-rank)
     hipStream_t d2h_stream = nullptr;   // host entry: output rows to the caller while kernels run
-    hipEvent_t ev_a = nullptr, ev_b = nullptr, ev_c = nullptr, ev_d = nullptr, ev_e = nullptr;
+    Event ev_a, ev_b, ev_c, ev_d, ev_e;
     std::mutex mu;
-    DevBuf b_src, b_dst, b_lat, b_loss, b_ids, b_nodes, b_olat, b_oloss;  // host-entry staging
+    DevBuf b_src, b_dst, b_lat, b_loss, b_nodes, b_olat, b_oloss;  // host-entry staging
     DevBuf b_W, b_WL, b_D, b_PRED, b_PRED2, b_L0, b_L1, b_mark, b_selfcnt, b_selflat, b_selfloss;
     DevBuf b_stats, b_flags, b_multi, b_pos, b_cnt;
     // sparse tight scan
-    DevBuf b_ecnt, b_eoff, b_indeg, b_cscoff, b_cscfill, b_entkey, b_entw, b_entb, b_grpu, b_grpe, b_cscent,
-        b_gblk, b_DST, b_scantmp, b_ess, b_rlen, b_roff;
+    DevBuf b_ecnt, b_eoff, b_indeg, b_cscoff, b_cscfill, b_entkey, b_entw, b_entb, b_grpe, b_cscent, b_DST,
+        b_scantmp, b_ess, b_rlen;
     // multi-rank: local sources, their output rows, exchange staging
     DevBuf b_lnodes, b_lpos, b_red, b_outoff, b_outdst;
     DevBuf b_cflags, b_tiles, b_tslot;  // symmetric FW: closure barrier words, own tiles, packed slots
@@ -850,13 +827,13 @@ struct srg_ctx {
     uint32_t sig_val[2] = {0, 0};
     bool hop_values = false;            // this build's hops use the signals (stream_hop)
     unsigned long long hop_bound_ticks = 200000000ull;  // a value hop's wait bound (100 MHz ticks; SymFw::begin)
-    hipEvent_t ev_fwreset = nullptr;    // SymFw::begin: the chain stream after the reset of the FW sync words
-    hipEvent_t ev_dst = nullptr;        // the scan's DST columns built (on the aux stream, beside the entry fill)
+    Event ev_fwreset;                   // SymFw::begin: the chain stream after the reset of the FW sync words
+    Event ev_dst;                       // the scan's DST columns built (on the aux stream, beside the entry fill)
     int fw_line_split = 0;              // symmetric FW: line sub-tiles per dimension (0 = auto) (SRG_OPT_FW_LINE_SPLIT)
     int fw_step = -1;                   // symmetric FW's line exchange between ranks (SRG_OPT_FW_STEP, chain_xmode)
     DevBuf b_xlb, b_xflags;             // line buffers (kept lines / the exchange's three), peers' arrival flags
     uint32_t xepoch = 0;                // device-side exchange: this build's flag value (agreed in share_ptrs)
-    std::vector<hipEvent_t> ev_ov;      // FW beside the H2D: one "chunk landed" event per chunk
+    std::vector<Event> ev_ov;           // FW beside the H2D: one "chunk landed" event per chunk
     uint32_t* kout_key = nullptr;       // this call's RoutingInfo key table on the device (key mode), and
     uint64_t* kout_diag = nullptr;      // its diagonal (raw self-loop latencies per position)
     DevBuf b_odiag;
@@ -867,33 +844,25 @@ struct srg_ctx {
     double ms_create_runtime = 0, ms_create_lib = 0;  // srg_create: HIP runtime / device init vs the library's own
     // packet-event batches (events.hip.h): key / index ping-pong buffers, tile histograms
     DevBuf b_ek0, b_ek1, b_eh0, b_eh1, b_ei0, b_ei1, b_ehist, b_eoffs, b_ered;
+    // Teardown.  The body releases what depends on order; the DevBuf and Event members free
+    // themselves afterwards (members are destroyed after the body), so device buffers go last.
+    // Every path that deletes a context has set its device on the calling thread first:
+    // srg_destroy (also srg_multi's teardown, rank by rank) and srg_create's failure path.
+    //   1. comm, before the streams its collectives were queued on
+    //   2. the hop signals, the late-loss ring, the mailbox
+    //   3. the streams (loss_stream is d2h_stream: destroyed once)
+    //   4. the host pool (joins its workers), then the codec's pinned ring they wrote
+    //   5. the pinned-table pool is closed; tables still held by a RoutingInfo free themselves
     ~srg_ctx() {
-        for (DevBuf* b : {&b_src, &b_dst, &b_lat, &b_loss, &b_ids, &b_nodes, &b_olat, &b_oloss, &b_W, &b_WL,
-                          &b_D, &b_PRED, &b_PRED2, &b_L0, &b_L1, &b_mark, &b_selfcnt, &b_selflat, &b_selfloss,
-                          &b_stats, &b_flags, &b_multi, &b_pos, &b_cnt, &b_ecnt, &b_eoff, &b_indeg, &b_cscoff,
-                          &b_cscfill, &b_entkey, &b_entw, &b_entb, &b_grpu, &b_grpe, &b_cscent, &b_gblk, &b_DST,
-                          &b_scantmp, &b_ess, &b_rlen, &b_roff, &b_lnodes, &b_lpos, &b_red, &b_cflags, &b_tiles, &b_tslot, &b_outoff, &b_outdst, &b_xlb, &b_xflags, &b_xexc, &b_odiag,
-                          &b_ek0, &b_ek1, &b_eh0, &b_eh1, &b_ei0, &b_ei1, &b_ehist, &b_eoffs, &b_ered})
-            b->release();
         delete comm;
-        for (hipEvent_t e : prof_events) (void)hipEventDestroy(e);
         for (uint32_t* p : sig)
             if (p) (void)hipFree(p);
-        for (hipEvent_t e : {ev_a, ev_b, ev_c, ev_d, ev_e, ev_ledges, ev_lin, ev_ldone, ev_wlate, ev_fwreset, ev_dst})
-            if (e) (void)hipEventDestroy(e);
-        for (hipEvent_t e : ev_ov) (void)hipEventDestroy(e);
-        for (hipEvent_t e : ev_lring)
-            if (e) (void)hipEventDestroy(e);
         if (h_lring) (void)hipHostFree(h_lring);
         if (hbox) (void)hipHostFree(hbox);
         for (hipStream_t s : {aux_stream, comm_stream, d2h_stream, stream})
             if (s) (void)hipStreamDestroy(s);
         delete pool;
-        for (hipEvent_t e : ev_ring)
-            if (e) (void)hipEventDestroy(e);
         if (h_ring) (void)hipHostFree(h_ring);
-        for (DevBuf* b : {&b_n16s, &b_n16d, &b_n32l, &b_DST2, &b_exc})
-            b->release();
         tpool->close();
     }
 };
@@ -964,6 +933,14 @@ uint32_t node_gml_id(const DevGraph& g, uint32_t v, hipStream_t st) {
     HIP_CHECK(hipMemcpyAsync(&id, g.ids_dev + v, 4, hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipStreamSynchronize(st));
     return id;
+}
+
+// at least n timed events in c.prof_events (SRG_OPT_PROFILING)
+void ensure_prof_events(srg_ctx& c, size_t n) {
+    while (c.prof_events.size() < n) {
+        c.prof_events.emplace_back();
+        c.prof_events.back().create_timed();
+    }
 }
 
 template <class F>
@@ -1253,8 +1230,17 @@ struct HostSink {
     }
     // wait for every copy; throws on a failed one
     void finish() {
-        if (kthread.joinable()) kthread.join();
+        drain();
         if (!kerr.empty()) fail(SRG_ERR_HIP, "key D2H: " + kerr);
+        HIP_CHECK(hipStreamSynchronize(cs));
+        if (!err.empty()) fail(SRG_ERR_HIP, "D2H copy: " + err);
+    }
+    ~HostSink() { drain(); }  // an exception unwound past finish(): drain before the buffers go away
+
+   private:
+    // both helper threads joined, every SDMA copy complete, the per-copy signals and events gone
+    void drain() {
+        if (kthread.joinable()) kthread.join();
         if (worker.joinable()) {
             {
                 std::lock_guard<std::mutex> lk(mu);
@@ -1270,24 +1256,6 @@ struct HostSink {
         sigs.clear();
         for (hipEvent_t e : evs) (void)hipEventDestroy(e);
         evs.clear();
-        HIP_CHECK(hipStreamSynchronize(cs));
-        if (!err.empty()) fail(SRG_ERR_HIP, "D2H copy: " + err);
-    }
-    ~HostSink() {  // an exception unwound past finish(): drain before the buffers go away
-        if (kthread.joinable()) kthread.join();
-        if (worker.joinable()) {
-            {
-                std::lock_guard<std::mutex> lk(mu);
-                closing = true;
-            }
-            cv.notify_one();
-            worker.join();
-        }
-        for (hsa_signal_t sg : sigs) {
-            hsa_signal_wait_scacquire(sg, HSA_SIGNAL_CONDITION_LT, 1, UINT64_MAX, HSA_WAIT_STATE_BLOCKED);
-            hsa_signal_destroy(sg);
-        }
-        for (hipEvent_t e : evs) (void)hipEventDestroy(e);
     }
 };
 
@@ -1378,48 +1346,6 @@ void stream_hop(srg_ctx& c, int i, hipStream_t from, hipStream_t to, hipEvent_t 
     HIP_CHECK(hipStreamWaitEvent(to, ev, 0));
 }
 
-// ---- distribution plan --------------------------------------------------
-// G ranks.  FW ownership: the general FW gives rank r the whole rows of the row blocks
-// [blk_lo[r], blk_lo[r+1]); the symmetric FW gives it the stored tiles (I, J) with
-// (I + J) mod G == r (fw_line_sym).  After FW every rank holds the whole D.  Sources: rank r
-// routes the used nodes at positions [p0, p1) = [n r / G, n (r+1) / G) of `nodes`, so its output
-// rows are one contiguous range whatever the node order.
-struct Plan {
-    int G = 1, g = 0, nb = 0, rb0 = 0, rb1 = 0;
-    std::vector<int> blk_lo;               // [G+1] first row block per rank (general FW)
-    uint32_t p0 = 0, p1 = 0;               // own sources = nodes[p0 .. p1)
-    std::vector<uint32_t> lnodes, lpos;    // own sources (vertex) and their output rows (p0 ..)
-    int owner(int b) const { return (int)(std::upper_bound(blk_lo.begin(), blk_lo.end(), b) - blk_lo.begin()) - 1; }
-    bool own(int b) const { return b >= rb0 && b < rb1; }
-};
-
-inline void tri_tile_h(int nb, int idx, int& I, int& J) {  // kernels.hip.h tri_tile, on the host
-    int i = 0;
-    while (i + 1 < nb && (i + 1) * nb - (i + 1) * i / 2 <= idx) ++i;
-    I = i;
-    J = i + (idx - (i * nb - i * (i - 1) / 2));
-}
-
-Plan make_plan(int G, int g, uint32_t V, int T, const std::vector<uint32_t>& nodes_h) {
-    Plan p;
-    p.G = G;
-    p.g = g;
-    p.nb = (int)(((size_t)V + T - 1) / T);
-    p.blk_lo.resize(G + 1);
-    for (int r = 0; r <= G; ++r) p.blk_lo[r] = (int)((int64_t)r * p.nb / G);
-    p.blk_lo[G] = p.nb;
-    p.rb0 = p.blk_lo[g];
-    p.rb1 = p.blk_lo[g + 1];
-    const uint64_t n = nodes_h.size();
-    p.p0 = (uint32_t)(n * g / G);
-    p.p1 = (uint32_t)(n * (g + 1) / G);
-    for (uint32_t q = p.p0; q < p.p1; ++q) {
-        p.lnodes.push_back(nodes_h[q]);
-        p.lpos.push_back(q);
-    }
-    return p;
-}
-
 // FW lookahead chain kernels raise their wave priority (s_setprio 3) beside the bulk tiles: C3 FW
 // 24.1 -> 23.5 ms (profiles/r02/prio; the option that turned it off was A/B only and is gone)
 constexpr int kChainPrio = 1;
@@ -1501,11 +1427,7 @@ void fw_blocked(srg_ctx& c, const Plan& pl, K* D, size_t Vp, hipStream_t st, uin
     const bool multi = c.comm && c.comm->nranks > 1;
     const bool prof = c.profiling && nb > 2;
     if (prof) {
-        while (c.prof_events.size() < (size_t)2 * nb) {
-            hipEvent_t e;
-            HIP_CHECK(hipEventCreate(&e));
-            c.prof_events.push_back(e);
-        }
+        ensure_prof_events(c, (size_t)2 * nb);
     }
     hipStream_t aux = c.aux_stream, cs = c.comm_stream;
     const size_t panel_bytes = (size_t)T * Vp * sizeof(K);
@@ -1602,48 +1524,6 @@ void fw_sym_finish(srg_ctx& c, const Plan& pl, K* D, size_t Vp, hipStream_t st, 
 
 // this rank's stored tiles (triangle indices, row-major; uploaded to c.b_tiles), and for the final
 // exchange every tile's slot in the packed buffer (owner-major, each owner's tiles in triangle order)
-// The bulk's launch order (SRG_OPT_FW_XCD_ORDER): workgroup b runs on XCD b % 8 (round-robin
-// dispatch), and row-major order deals consecutive tiles of a block-row -- which share their row
-// operand LB[I] -- to 8 different XCDs, so every XCD's L2 fetches nearly every line-buffer tile of
-// the pivot.  Here the tiles are sorted along a Z-order (Morton) curve of (I, J) and cut into 8
-// contiguous runs, XCD x taking run x: each XCD works on a compact block of the triangle and reads
-// only that block's rows and columns of LB.  Slots past a short run hold -1 (skipped).  One list per
-// pivot kb without the tiles of lines kb and kb + 1 (the chain's), so the 8 runs stay equal: with
-// those tiles returning early inside one list, the XCDs whose blocks hold line kb idled (measured
-// 4 % slower than triangle order).
-inline uint32_t morton2(uint32_t a, uint32_t b) {
-    uint32_t z = 0;
-    for (int i = 0; i < 16; ++i) z |= ((a >> i) & 1u) << (2 * i + 1) | ((b >> i) & 1u) << (2 * i);
-    return z;
-}
-inline void xcd_tile_order(const std::vector<int>& own, int nb, std::vector<int>& out, std::vector<int>& off) {
-    struct Z {
-        uint32_t key;
-        int t, I, J;
-        bool operator<(const Z& o) const { return key < o.key; }
-    };
-    std::vector<Z> z(own.size());
-    for (size_t i = 0; i < own.size(); ++i) {
-        int I, J;
-        tri_tile_h(nb, own[i], I, J);
-        z[i] = {morton2((uint32_t)I, (uint32_t)J), own[i], I, J};
-    }
-    std::sort(z.begin(), z.end());
-    out.clear();
-    off.assign(nb + 1, 0);
-    std::vector<int> run;
-    for (int kb = 0; kb < nb; ++kb) {
-        const int k1 = kb + 1;
-        run.clear();
-        for (const Z& q : z)
-            if (q.I != kb && q.J != kb && q.I != k1 && q.J != k1) run.push_back(q.t);
-        const size_t per = (run.size() + 7) / 8, base = out.size();
-        out.resize(base + per * 8, -1);
-        for (size_t i = 0; i < run.size(); ++i) out[base + (i % per) * 8 + i / per] = run[i];
-        off[kb + 1] = (int)out.size();
-    }
-}
-
 inline void sym_tiles(srg_ctx& c, const Plan& pl, hipStream_t st, std::vector<int>& own_h, std::vector<int>& slot_h,
                       std::vector<int>& first, std::vector<int>& bulk_off) {
     const int nb = pl.nb, G = pl.G, g = pl.g;
@@ -1736,9 +1616,9 @@ struct SymFw {
         prof_relax = &relax;
         prof_n = &n;
         {
-            const char* hv = std::getenv("SRG_STREAM_HOPS");
+            const bool events = srg_env::stream_hops_events();
             std::lock_guard<std::mutex> lk(g_dev_mu);
-            c.hop_values = g_dev_ctx[c.device] == 1 && !(hv && std::strcmp(hv, "events") == 0);
+            c.hop_values = g_dev_ctx[c.device] == 1 && !events;
         }
         lds_bulk = lb_lds<K, T, KCS>();
         set_lds(fw_bulk_lb<K, T, KCS>, lds_bulk);
@@ -1758,11 +1638,11 @@ struct SymFw {
         // a bulk below one round of the slots (3 per CU) runs as quadrants (fw_bulk_lb_q): sim 8:0
         // bulk launch 59.5 -> 48.6 us, FW 6.24-6.28 -> 6.02-6.04 ms (profiles/r05/chain/)
         // (one rank too: C2, nb = 32, 528 tiles; SRG_FW_BULK_Q = 0 / 1 forces it off / on for A/B)
-        const char* bq = std::getenv("SRG_FW_BULK_Q");
-        if (sizeof(K) == 4 && T == 128 && !(bq && bq[0] == '0')) {
+        const int bq = srg_env::fw_bulk_q();
+        if (sizeof(K) == 4 && T == 128 && bq != 0) {
             int cus = 256;
             HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c.device));
-            if (bulk_tiles < 3 * cus || (bq && bq[0] == '1')) {
+            if (bulk_tiles < 3 * cus || bq == 1) {
                 bulk_split = 2;
                 set_lds(fw_bulk_lb_q<K, T, 32>, lb_lds<K, T / 2, 32>());
             }
@@ -1772,11 +1652,7 @@ struct SymFw {
         set_lds(fw_line_lb<K, T, 4>, lb_lds<K, T / 4, line_kc<4>()>());
         prof = c.profiling && nb > 2;
         if (prof) {
-            while (c.prof_events.size() < (size_t)2 * nb) {
-                hipEvent_t e;
-                HIP_CHECK(hipEventCreate(&e));
-                c.prof_events.push_back(e);
-            }
+            ensure_prof_events(c, (size_t)2 * nb);
         }
         if (keep_lines) lball = (K*)c.b_xlb.get((size_t)nb * nb * TT * sizeof(K));
         else if (xmode) {  // one block of three (the peers' stores address it by offset)
@@ -2133,7 +2009,7 @@ struct FwOverlap {
         fw->keep_lines = true;
         on = true;
         ok = true;
-        dbg = std::getenv("SRG_DEBUG_OVERLAP") != nullptr;
+        dbg = srg_env::debug_overlap();
         if (dbg) e0 = tev(hs);
         enq = std::thread([this]() { run(); });
     }
@@ -2211,9 +2087,8 @@ struct FwOverlap {
         HIP_CHECK(hipGetLastError());
         // one event per chunk (the FW thread may not have waited on the previous one yet)
         if (nev == c->ev_ov.size()) {
-            hipEvent_t e;
-            HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            c->ev_ov.push_back(e);
+            c->ev_ov.emplace_back();
+            c->ev_ov.back().create();
         }
         hipEvent_t ev = c->ev_ov[nev++];
         HIP_CHECK(hipEventRecord(ev, hs));
@@ -2271,877 +2146,8 @@ struct FwOverlap {
     }
 };
 
-// Dense path for key type K. Returns false (u32 only) when certification fails.
-template <class K, int T>
-bool run_dense(srg_ctx& c, const DevGraph& g, const Plan& pl, const uint32_t* nodes, uint32_t n, uint64_t* out_lat,
-               float* out_loss, hipStream_t st, const Prelude& P, srg_stats* stats, HostSink* sink,
-               FwOverlap* ov = nullptr) {
-    // the FW already ran beside the H2D (FwOverlap): W, D and the closed D are in place
-    const bool pre = ov && ov->on && ov->ok && ov->ended && sizeof(K) == 4 && T == FwOverlap::T;
-    if (sizeof(K) == 8 && c.kout_key) {  // a key table needs the u32 keys
-        // (the host entry's internal key shipping just falls back to the u64 latency rows)
-        if (!(sink && sink->widen)) fail(SRG_INTERNAL_NEED_U64, "the build needs u64 latency keys: no u32 key table");
-        sink->widen = false;
-        c.kout_key = nullptr;
-        c.kout_diag = nullptr;
-    }
-    const uint32_t V = g.V;
-    const size_t Vp = ((size_t)V + T - 1) / T * T;
-    const size_t VV = Vp * Vp;
-    const bool multi = c.comm && c.comm->nranks > 1;
-    Timer tm(st);
-    c.own_row0 = pl.p0;  // this rank's output rows (the host entry ships only these without the exchange)
-    c.own_row1 = pl.p1;
-
-    K* W = (K*)c.b_W.get(VV * sizeof(K));
-    uint32_t* WL = (uint32_t*)c.b_WL.get(VV * 4);
-    K* D = (K*)c.b_D.get(VV * sizeof(K));
-    bool wl_late = false;  // late loss: WL is built after FW, once the losses have landed
-    if (pre) {
-        wl_late = g.late && !g.late->applied;
-    } else if constexpr (sizeof(K) == 4) {
-        // packed (latency, loss) keys: one atomic pass, then a tiled symmetrize + split pass
-        static_assert(T % 64 == 0, "tile");
-        unsigned long long* KW = (unsigned long long*)c.b_PRED.get(VV * 8);
-        HIP_CHECK(hipMemsetAsync(KW, 0xFF, VV * 8, st));
-        wl_late = g.late && !g.late->applied;
-        if (g.E) k_w_key<<<grid_for(g.E), kThreads, 0, st>>>(g.E, g.src, g.dst, g.lat, P.unit, wl_late ? nullptr : g.loss, KW, Vp);
-        const unsigned nb64 = (unsigned)(Vp / 64);
-        k_w_split<false><<<dim3(nb64, nb64), 256, 0, st>>>(KW, Vp, g.directed, (uint32_t*)W, WL, (uint32_t*)D);
-    } else {
-        loss_arrive(g, P.selfloss, st);
-        k_fill<K><<<grid_for(VV), kThreads, 0, st>>>(W, VV, KeyOps<K>::INF);
-        HIP_CHECK(hipMemsetAsync(WL, 0xFF, VV * 4, st));
-        if (g.E) {
-            k_w_lat<K><<<grid_for(g.E), kThreads, 0, st>>>(g.E, g.src, g.dst, g.lat, P.unit, g.directed, W, Vp);
-            k_w_loss<K><<<grid_for(g.E), kThreads, 0, st>>>(g.E, g.src, g.dst, g.lat, P.unit, g.loss, g.directed, W, WL,
-                                                             Vp);
-        }
-        k_init_d<K><<<grid_for(VV), kThreads, 0, st>>>(W, D, Vp);
-    }
-    // local sources and their output rows
-    const uint32_t nloc = (uint32_t)pl.lnodes.size();
-    uint32_t* lnodes = (uint32_t*)c.b_lnodes.get(std::max<size_t>(nloc, 1) * 4);
-    uint32_t* lpos = (uint32_t*)c.b_lpos.get(std::max<size_t>(nloc, 1) * 4);
-    if (nloc) {
-        HIP_CHECK(hipMemcpyAsync(lnodes, pl.lnodes.data(), (size_t)nloc * 4, hipMemcpyHostToDevice, st));
-        HIP_CHECK(hipMemcpyAsync(lpos, pl.lpos.data(), (size_t)nloc * 4, hipMemcpyHostToDevice, st));
-    }
-    HIP_CHECK(hipGetLastError());
-    const double ms_build = tm.lap();
-
-    // ---- blocked Floyd-Warshall; afterwards every rank holds the whole D ----
-    uint64_t prof_relax = 0;
-    int prof_n = 0;
-    double ms_dx = 0;  // multi-rank: D exchange at the end of FW (inside ms_fw, also in ms_exchange)
-    if (pre) {
-        prof_relax = ov->prof_relax;
-        prof_n = ov->prof_n;
-    } else if (sym_fw_for<K, T>(c, g)) {
-        if constexpr ((sizeof(K) == 4 && T == 128) || (sizeof(K) == 8 && T == 64))
-            fw_line_sym<K, T>(c, pl, D, Vp, st, prof_relax, prof_n, ms_dx);
-    } else {
-        // u32 keys: the pair-packed tile (two relaxations per 64-bit add + v_min3); the add + min3
-        // tile (PK = 0) ran the same C3 launch in 0.304 instead of 0.242 ms (profiles/r02c/fw_fold.txt)
-        // and is kept for u64 keys only
-        if constexpr (sizeof(K) == 4) fw_blocked<K, T, 2>(c, pl, D, Vp, st, prof_relax, prof_n);
-        else fw_blocked<K, T, 0>(c, pl, D, Vp, st, prof_relax, prof_n);
-        if (multi) gather_rows<K>(c, pl, D, Vp, T, st, ms_dx);
-    }
-    HIP_CHECK(hipGetLastError());
-    if (sym_fw_for<K, T>(c, g)) rb_async(c, MS_TIMEOUT, c.fw_timeout, st);  // read after FW, on its stream
-    const double ms_fw = tm.lap();
-    if (sym_fw_for<K, T>(c, g) && rb_get<uint32_t>(c, MS_TIMEOUT))
-        fail(SRG_ERR_HIP, fw_timeout_message(rb_get<uint32_t>(c, MS_TIMEOUT)));
-#ifdef SRG_TEST_HOOKS
-    if (c.test_fault == 1)  // TEST HOOK (SRG_OPT_TEST_FAULT): a lost synchronisation's result, for the guard
-        HIP_CHECK(hipMemsetAsync(D, 0, VV * sizeof(K), st));
-#endif
-    if (wl_late) {
-        // WL = min loss among the min-latency parallel edges (what k_w_split gives), from the
-        // losses that crossed PCIe during FW.  Built here, after FW, rather than beside it: on a
-        // narrow grid beside the FW tiles it cost the bulk launches 5 % (0.242 -> 0.255 ms,
-        // FW +0.8 ms, profiles/r02g) for about the same total.
-        // The packed-key pass again, now with the losses (its buffer is free until the scan
-        // writes PRED), splitting out WL only: 0.8 ms where k_w_loss's random W reads took 2.3.
-        // It runs on the (idle) FW lookahead stream beside the certification, extract and
-        // essential-entry count, which read W and D only; st waits for it before the entry fill.
-        hipStream_t ax = c.aux_stream;  // st is synchronised (tm.lap): FW is complete
-        const auto tl0 = std::chrono::steady_clock::now();
-        loss_arrive(g, P.selfloss, ax);
-        if (std::getenv("SRG_DEBUG_OVERLAP"))
-            std::fprintf(stderr, "late loss: the host waited %.2f ms for the loss thread after FW\n",
-                         std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tl0).count());
-        if constexpr (sizeof(K) == 4) {
-            unsigned long long* KW = (unsigned long long*)c.b_PRED.get(VV * 8);
-            HIP_CHECK(hipMemsetAsync(KW, 0xFF, VV * 8, ax));
-            if (g.E) k_w_key<<<grid_for(g.E), kThreads, 0, ax>>>(g.E, g.src, g.dst, g.lat, P.unit, g.loss, KW, Vp);
-            const unsigned nb64 = (unsigned)(Vp / 64);
-            k_w_split<true><<<dim3(nb64, nb64), 256, 0, ax>>>(KW, Vp, g.directed, nullptr, WL, nullptr);
-            HIP_CHECK(hipGetLastError());
-        }
-        HIP_CHECK(hipEventRecord(c.ev_wlate, ax));
-    }
-    if (prof_n && stats) {
-        double sum = 0;
-        for (int i = 0; i < prof_n; ++i) {
-            float ms = 0;
-            HIP_CHECK(hipEventElapsedTime(&ms, c.prof_events[2 * i], c.prof_events[2 * i + 1]));
-            sum += ms;
-        }
-        stats->prof_launches += prof_n;
-        stats->prof_kernel_ms += sum;
-        stats->prof_relaxations += prof_relax;
-    }
-
-    // Every collective after FW runs on the comm stream, in the same order on every rank:
-    // allreduce(certify) -> allreduce(unreachable) -> allgather(latency rows, overlapped with
-    // the scan) -> allgather(essential bitmask) -> allgather(loss rows).
-    hipStream_t cs = c.comm_stream;
-    auto cs_after_st = [&]() {
-        HIP_CHECK(hipEventRecord(c.ev_a, st));
-        HIP_CHECK(hipStreamWaitEvent(cs, c.ev_a, 0));
-    };
-    auto st_after_cs = [&]() {
-        HIP_CHECK(hipEventRecord(c.ev_b, cs));
-        HIP_CHECK(hipStreamWaitEvent(st, c.ev_b, 0));
-    };
-    auto reduce_flag = [&](uint32_t* flag_dev) -> uint32_t {
-        uint32_t* red = (uint32_t*)c.b_red.get(16);
-        HIP_CHECK(hipMemcpyAsync(red, flag_dev, 4, hipMemcpyDeviceToDevice, st));
-        if (multi) {
-            cs_after_st();
-            c.comm->allreduce_max_u32(red, 1, cs);
-            st_after_cs();
-        }
-        rb_async(c, MS_REDUCE, red, st);
-        HIP_CHECK(hipStreamSynchronize(st));
-        return rb_get<uint32_t>(c, MS_REDUCE);
-    };
-    // output rows of every rank: positions [n r / G, n (r+1) / G)
-    const bool exchange = multi && c.gather_output;
-    auto exchange_rows = [&](void* out, size_t elem) {  // on cs, after st
-        const size_t row = (size_t)n * elem;
-        std::vector<size_t> offs(pl.G), lens(pl.G);
-        for (int r = 0; r < pl.G; ++r) {
-            const size_t a = (uint64_t)n * r / pl.G, b = (uint64_t)n * (r + 1) / pl.G;
-            offs[r] = a * row;
-            lens[r] = (b - a) * row;
-        }
-        cs_after_st();
-        c.comm->allgatherv(out, offs.data(), lens.data(), cs);
-    };
-
-    // ---- essential edges (W[u][t] == D[u][t]) counted into the scan's pair-record layout ----
-    // One rank: on the comm stream (idle after the H2D), beside the certification / extract and
-    // their flag read-backs on st, which read D only; several ranks: on st (cs carries collectives).
-    hipStream_t es = multi ? st : c.comm_stream;
-    auto drain_es = [&]() {  // (before an early return: a rerun may reallocate these buffers)
-        if (es != st) HIP_CHECK(hipStreamSynchronize(es));
-    };
-    constexpr int TS = 64;
-    constexpr int VE = 16 / (int)sizeof(K);
-    const size_t nmax = std::max<uint32_t>(nloc, 1);
-    uint32_t* PRED = (uint32_t*)c.b_PRED.get(nmax * Vp * 4);
-    unsigned long long* multi_cnt = (unsigned long long*)c.b_multi.get(8);
-    int rounds = 0;
-    unsigned long long nmulti = 0;
-    uint64_t n_ess = 0;
-    int scan_kind = SRG_SCAN_NONE;
-    bool loss_written = false;  // out_loss already filled by the per-row kernel
-    float* Lfin = nullptr;
-    double ms_scan = 0;
-    HIP_CHECK(hipMemsetAsync(multi_cnt, 0, 8, st));
-    // essential bitmask (V^2/8 bytes): every rank holds the whole D and W, so each builds all of it
-    const uint32_t nw64 = (V + 63) / 64;
-    unsigned long long* ess = (unsigned long long*)c.b_ess.get((size_t)V * nw64 * 8);
-    k_ess_mask<K><<<V, 256, 0, es>>>(W, D, Vp, V, 0u, V, nw64, ess);
-    uint32_t* indeg = (uint32_t*)c.b_indeg.get(((size_t)nw64 * 64 + 1) * 4);
-    uint32_t* cscoff = (uint32_t*)c.b_cscoff.get(((size_t)nw64 * 64 + 1) * 4);
-    HIP_CHECK(hipMemsetAsync(indeg, 0, ((size_t)nw64 * 64 + 1) * 4, es));
-    // pair-lane LDS scan (tight_v5); u64 keys run it on the keys' low words (exact together with
-    // the loss pass's multi-predecessor check, tight_sparse.hip.h)
-    const bool v5lo = sizeof(K) == 8;
-    const uint32_t SB = V5_SB;
-    const size_t npad = ((size_t)nloc + SB - 1) / SB * SB;
-    const size_t dst_bytes = (size_t)nw64 * 64 * std::max<size_t>(npad, 64) * sizeof(K);
-    const uint32_t NT = nw64 * 64;
-    const uint32_t nK5 = (V + V5_UC - 1) / V5_UC, nbTT5 = (NT + V5_TT - 1) / V5_TT;
-    const size_t NG5 = (size_t)nbTT5 * nK5 * V5_WAVES;
-    uint32_t* v5_cnt = (uint32_t*)c.b_ecnt.get((size_t)nbTT5 * nK5 * V5_TT * 4);
-    uint32_t* v5_goff = (uint32_t*)c.b_eoff.get((NG5 + 1) * 4);
-    uint64_t E_ess = 0, E_layout = 0;
-    {
-        uint32_t* v5_glen = (uint32_t*)c.b_rlen.get((NG5 + 1) * 4);
-        HIP_CHECK(hipMemsetAsync(v5_cnt, 0, (size_t)nbTT5 * nK5 * V5_TT * 4, es));
-        HIP_CHECK(hipMemsetAsync(v5_glen, 0, (NG5 + 1) * 4, es));
-        const size_t nwaves = (size_t)nw64 * nK5;
-        k_v5_count<<<(unsigned)((nwaves * 64 + 255) / 256), 256, 0, es>>>(ess, V, nw64, nK5, v5_cnt, v5_glen, indeg);
-        HIP_CHECK(hipGetLastError());
-        size_t ta = 0, tc = 0;
-        HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, ta, indeg, cscoff, (int)(NT + 1), es));
-        HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, tc, v5_glen, v5_goff, (int)(NG5 + 1), es));
-        const size_t tbytes = std::max(ta, tc);
-        void* tmp = c.b_scantmp.get(tbytes);
-        HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(tmp, ta, indeg, cscoff, (int)(NT + 1), es));
-        HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(tmp, tc, v5_glen, v5_goff, (int)(NG5 + 1), es));
-        HIP_CHECK(hipGetLastError());
-    }
-
-    // u32 certification: no saturated key in any used row (every rank must agree)
-    HIP_CHECK(hipMemsetAsync(&P.flags->inf_in_used_row, 0, 4, st));
-    HIP_CHECK(hipMemsetAsync(&P.flags->impossible, 0, 4, st));
-    if (nloc)
-        k_certify<K><<<nloc, kThreads, 0, st>>>(
-            D, Vp, lnodes, nloc, nodes, n,
-            // (an edge of >= INF keys counts as absent: the bound is never above INF, which stays legal)
-            (K)std::min<uint64_t>(min_edge_key(P.es.min_lat_inv, P.unit), (uint64_t)KeyOps<K>::INF), P.flags);
-    // (a simulated rank -- SRG_OPT_SIMULATE_RANK, timing only -- never receives its peers' line
-    // segments, so its table is not a result and the guard does not apply)
-    const bool simulated = c.comm && std::strcmp(c.comm->kind(), "simulated") == 0;
-    // both of k_certify's flags with one read-back when one rank (each read-back is a stream drain)
-    uint32_t impossible = 0, inf_any = 0;
-    if (multi) {
-        impossible = reduce_flag(&P.flags->impossible);
-        inf_any = reduce_flag(&P.flags->inf_in_used_row);
-    } else {
-        rb_async(c, MS_REDUCE, &P.flags->impossible, st);
-        rb_async(c, MS_REDUCE2, &P.flags->inf_in_used_row, st);
-        HIP_CHECK(hipStreamSynchronize(st));
-        impossible = rb_get<uint32_t>(c, MS_REDUCE);
-        inf_any = rb_get<uint32_t>(c, MS_REDUCE2);
-    }
-    if (impossible && !simulated)
-        fail(SRG_ERR_INTERNAL, "FW produced an impossible table: a used pair's latency is below the smallest edge "
-                               "latency (" + std::to_string(~P.es.min_lat_inv) + " ns)");
-    if (sizeof(K) == 4 && inf_any) {
-        // a used pair at INF: unreachable -- unless some path could reach 2^31-1 ns, in which case
-        // the u64 keys decide (the u32 FW work is redone)
-        const unsigned __int128 bound = (unsigned __int128)P.max_key * (V > 1 ? V - 1 : 1);
-        if (bound >= KeyOps<uint32_t>::INF) {
-            if (wl_late) HIP_CHECK(hipStreamWaitEvent(st, c.ev_wlate, 0));  // the u64 rerun rewrites WL
-            drain_es();
-            return false;
-        }
-        fail(SRG_ERR_UNREACHABLE,
-             "assertion `left == right` failed: paths.len() != nodes.len().pow(2) (a used node is unreachable "
-             "from another used node)");
-    }
-    if (P.wrap_risk) {
-        // max edge latency x V reaches 2^64 ns: check that no relaxation the reference runs wraps
-        // its u64 sum (k_wrap_edges), and that outputs D * unit fit u64 (they are below such a sum)
-        const unsigned __int128 bound = (unsigned __int128)P.max_key * (V > 1 ? V - 1 : 1);
-        const bool inf_known = sizeof(K) == 4 ? bound < KeyOps<uint32_t>::INF : !P.range_risk;
-        HIP_CHECK(hipMemsetAsync(&P.flags->wrap, 0, 8, st));
-        for (uint32_t r0 = 0; r0 < nloc && g.E; r0 += 32768) {
-            const uint32_t nr = std::min<uint32_t>(32768, nloc - r0);
-            k_wrap_edges<K><<<dim3(grid_for(g.E, 64), nr), 256, 0, st>>>(g.E, g.src, g.dst, g.lat, g.directed, D, Vp,
-                                                                        lnodes + r0, P.unit, inf_known ? 1 : 0, P.flags);
-        }
-        HIP_CHECK(hipGetLastError());
-        const uint32_t wrapped = reduce_flag(&P.flags->wrap);
-        if (wrapped)
-            fail(SRG_ERR_LATENCY_RANGE, "a shortest-path relaxation sums past 2^64 ns (max edge latency " +
-                                            std::to_string(P.es.max_lat) +
-                                            " ns): the reference's u64 latency sum would wrap (mod.rs:327)");
-        if (reduce_flag(&P.flags->wrap_inf)) {
-            if (sizeof(K) == 4) {  // a vertex past the u32 keys: decide on the u64 keys
-                if (wl_late) HIP_CHECK(hipStreamWaitEvent(st, c.ev_wlate, 0));
-                drain_es();
-                return false;
-            }
-            fail(SRG_ERR_LATENCY_RANGE, "a vertex has no path below 2^62 latency units on a graph whose u64 latency "
-                                        "sums can wrap (max edge latency " +
-                                            std::to_string(P.es.max_lat) + " ns)");
-        }
-    }
-
-    // latency outputs (+ diagonal self-loops) of the own rows, right after FW
-    HIP_CHECK(hipMemsetAsync(&P.flags->unreachable_used_pair, 0, 4, st));
-    // k_extract_ident moves rows by 16-B vectors: the caller's arrays (a device-entry torch view may be
-    // offset) must be 16-B aligned too (row offsets are, since n % 4 == 0)
-    const bool al16 = (((uintptr_t)out_lat | (uintptr_t)c.kout_key) & 15u) == 0;
-    if (nloc && P.ident && n % 4 == 0 && al16)
-        k_extract_ident<K><<<nloc, 256, 0, st>>>(D, Vp, lnodes, n, P.selflat, out_lat, P.flags, P.unit, c.kout_key,
-                                                 c.kout_diag);
-    else if (nloc)
-        k_extract<K><<<nloc, kThreads, 0, st>>>(D, nullptr, Vp, lnodes, nloc, nodes, n, lpos,
-                                                                      P.selflat, P.selfloss, out_lat, out_loss,
-                                                                      P.flags, 1, P.unit, c.kout_key, c.kout_diag);
-    HIP_CHECK(hipGetLastError());
-    if (reduce_flag(&P.flags->unreachable_used_pair)) {
-        if (sizeof(K) == 8 && P.range_risk)
-            fail(SRG_ERR_LATENCY_RANGE, "a used pair has no path below 2^62 latency units (max edge latency " +
-                                            std::to_string(P.es.max_lat) +
-                                            " ns): unreachable, or a latency sum the reference's u64 would wrap");
-        fail(SRG_ERR_UNREACHABLE,
-             "assertion `left == right` failed: paths.len() != nodes.len().pow(2) (a used node is unreachable "
-             "from another used node)");
-    }
-    if (exchange) exchange_rows(out_lat, 8);  // overlaps the scan and the loss pass below
-    // host entry, own rows only (one rank, or several without the exchange): the latency rows are
-    // final -- they leave during the scan / loss pass
-    const bool sink_rows = sink && !exchange && nloc && sink->ok();
-    if (sink && c.kout_key) sink->key_unit = P.unit;
-    if (sink_rows) {
-        if (c.kout_key && sink->widen) sink->send_keys(st, c.kout_key, pl.p0, nloc, P.unit);  // (widened on the host)
-        else if (c.kout_key) sink->send_rows(st, c.kout_key, sink->lat, pl.p0, nloc, 4);  // (sink->lat: the host key table)
-        else sink->send_rows(st, out_lat, sink->lat, pl.p0, nloc, 8);
-        sink->lat_sent = true;
-    }
-
-    // ---- tight-predecessor scan, loss (the essential entries were counted above) ----
-    {
-        rb_async(c, MS_TAIL0, cscoff + NT, es);
-        rb_async(c, MS_TAIL1, v5_goff + NG5, es);
-        HIP_CHECK(hipStreamSynchronize(es));
-        E_ess = rb_get<uint32_t>(c, MS_TAIL0);
-        E_layout = 2ull * rb_get<uint32_t>(c, MS_TAIL1);
-    }
-    n_ess = E_ess;
-    if (wl_late) HIP_CHECK(hipStreamWaitEvent(st, c.ev_wlate, 0));  // WL (late loss) before the entry fill
-    const bool sparse = (double)E_ess <= c.sparse_threshold * (double)V * (double)V &&
-                        E_layout + 256 < 0xF0000000ull && dst_bytes < 0xFFFFFFFFull;
-    if (sparse) {
-        scan_kind = SRG_SCAN_SPARSE;
-        // the scan's DST (D columns of the used sources, + their low words for u64 keys) on the aux
-        // stream, beside the entry fill: it reads D only (st is past FW)
-        K* DST = nullptr;
-        const uint32_t* DSTs = nullptr;
-        uint32_t dsts_bytes = 0;
-        if (nloc) {
-            hipStream_t ax = c.aux_stream;
-            const uint32_t nbS = (uint32_t)(npad / 64);
-            DST = (K*)c.b_DST.get(dst_bytes);
-            k_build_dst<K><<<dim3(nw64, nbS), 256, 0, ax>>>(D, Vp, lnodes, nloc, DST, npad);
-            DSTs = (const uint32_t*)DST;
-            dsts_bytes = (uint32_t)std::min<size_t>(dst_bytes, 0xFFFFFFFFull);
-            if (v5lo) {
-                const size_t cnt = dst_bytes / 8;
-                uint32_t* lo = (uint32_t*)c.b_DST2.get(cnt * 4);
-                k_low_words<<<grid_for(cnt), kThreads, 0, ax>>>(reinterpret_cast<const uint64_t*>(DST), cnt, lo);
-                DSTs = lo;
-                dsts_bytes = (uint32_t)(cnt * 4);
-            }
-            HIP_CHECK(hipGetLastError());
-            HIP_CHECK(hipEventRecord(c.ev_dst, ax));
-        }
-        const size_t Eb = E_layout + 256;
-        uint32_t* cscpos = (uint32_t*)c.b_cscfill.get((size_t)nbTT5 * nK5 * V5_TT * 4);
-        K* ent_w = (K*)c.b_entw.get(Eb * sizeof(K));
-        uint2* ent_ub = (uint2*)c.b_grpe.get(Eb * 8);  // {u, 1 - loss bits}: one gather in the loss pass
-        uint32_t* cscent = (uint32_t*)c.b_cscent.get(std::max<uint64_t>(E_ess, 1) * 4);
-        k_v5_cscpos<<<(NT + 255) / 256, 256, 0, st>>>(v5_cnt, cscoff, NT, nK5, cscpos);
-        uint2* rec = (uint2*)c.b_entkey.get((Eb + V5_SLACK) * 8);
-        {
-            const size_t nwaves = (size_t)nw64 * nK5;
-            k_v5_fill<K><<<(unsigned)((nwaves * 64 + 255) / 256), 256, 0, st>>>(ess, W, WL, Vp, V, nw64, nK5, v5_cnt,
-                                                                                  v5_goff, cscpos, rec, ent_w,
-                                                                                  ent_ub, cscent);
-        }
-        HIP_CHECK(hipGetLastError());
-        // host entry, one rank, per-row LDS loss: scan groups interleaved with the loss rows
-        const size_t lds_rows = loss_rows_lds(V);
-        const uint32_t scan_groups = c.scan_groups ? (uint32_t)c.scan_groups : 3u;
-        const bool interleave = sink_rows && lds_rows <= 150 * 1024 && scan_groups > 1;
-        if (interleave) {
-            set_lds(k_loss_rows<K, true>, lds_rows);
-            HIP_CHECK(hipMemsetAsync(&P.flags->changed, 0, 4, st));
-        }
-        // the per-row LDS loss pass reads PRED packed with each single predecessor's {u, 1 - loss}
-        // (k_pred_pack, after each scan group); the global-memory fold the entry indices
-        uint32_t* PREDK = lds_rows <= 150 * 1024 ? (uint32_t*)c.b_PRED2.get(nmax * Vp * 8) : nullptr;
-        auto pack_pred = [&](uint32_t r0, uint32_t r1) {
-            const uint32_t nsb = (r1 - r0 + 127) / 128, nt8 = (nbTT5 + 7) / 8;
-            k_pred_pack<<<8u * nt8 * nsb, 256, 0, st>>>(PRED, Vp, r0, r1, NT, nbTT5, nsb, ent_ub, (uint2*)PREDK,
-                                                        multi_cnt);
-            HIP_CHECK(hipGetLastError());
-        };
-        if (nloc) {
-            HIP_CHECK(hipStreamWaitEvent(st, c.ev_dst, 0));  // (the scan's DST, built on the aux stream)
-            const uint32_t inf_check = v5lo ? 0u : 1u;
-            const uint32_t nbS5 = (uint32_t)(npad / SB);
-            // host entry: the scan runs in source-block groups, each group's loss rows folded right
-            // after it and shipped while later groups scan (loss rows on a second stream beside the
-            // next group's scan were starved of CUs: 24.7 ms vs 20.8)
-            const uint32_t ng = interleave ? std::min<uint32_t>(scan_groups, nbS5) : 1u;
-            for (uint32_t gi = 0; gi < ng; ++gi) {
-                // group bounds on multiples of 8 source blocks: every XCD gets the same number of
-                // blocks per launch (20 blocks = 3/3/3/3/2/2/2/2 ran 33 % long)
-                auto cut = [&](uint32_t q) {
-                    if (q == 0) return 0u;
-                    if (q == ng) return nbS5;
-                    // three groups: half, then all but the last partial 8 blocks, so the loss rows
-                    // left to ship after the last fold are few (C3 40 / 32 / 7 blocks: exposed D2H
-                    // 1.8 -> 0.8 ms, scan + tail -0.6 ms vs thirds, profiles/r02i/scan_cuts.txt)
-                    const uint32_t half = std::min(nbS5, (nbS5 / 2 + 4) / 8 * 8), last = (nbS5 - 1) / 8 * 8;
-                    if (ng == 3 && half > 0 && last > half) return q == 1 ? half : last;
-                    return std::min(nbS5, (nbS5 * q / ng + 4) / 8 * 8);
-                };
-                const uint32_t c0 = cut(gi), c1 = cut(gi + 1);
-                if (c1 == c0) continue;
-                const uint32_t nblk = (nbTT5 + 3) / 4 * ((c1 - c0 + 7) / 8);
-                tight_v5<<<8u * 32u * ((nblk + 7) / 8), V5_WAVES * 64, 0, st>>>(
-                    DSTs, npad, dsts_bytes, lnodes, nloc, V, NT, nbTT5, c1, nK5, c0, v5_goff,
-                    (const uint32_t*)c.b_entkey.get(0), PRED, Vp, inf_check);
-                HIP_CHECK(hipGetLastError());
-                if (interleave) {
-                    const uint32_t r0 = c0 * SB, r1 = std::min<uint32_t>(c1 * SB, nloc);
-                    if (r1 <= r0) continue;
-                    pack_pred(r0, r1);
-                    k_loss_rows<K, true><<<r1 - r0, 1024, lds_rows, st>>>(PREDK, Vp, V, lnodes, nloc, ent_ub, ent_w,
-                                                                   DST, npad, cscoff, cscent, P.selfloss, nodes, n,
-                                                                   lpos, out_loss, &P.flags->changed, r0);
-                    HIP_CHECK(hipGetLastError());
-                    sink->send_rows(st, out_loss, sink->loss, pl.p0 + r0, r1 - r0, 4);
-                }
-            }
-            if (!PREDK) k_count_multi<<<nloc, kThreads, 0, st>>>(PRED, nloc, V, Vp, multi_cnt);  // (else k_pred_pack counted)
-            HIP_CHECK(hipGetLastError());
-            ms_scan = tm.lap();
-            if (interleave) {  // loss rows already folded and shipped, group by group
-                sink->loss_sent = true;
-                rb_async(c, MS_CHANGED, &P.flags->changed, st);
-                HIP_CHECK(hipStreamSynchronize(st));
-                rounds = (int)rb_get<uint32_t>(c, MS_CHANGED);
-                loss_written = true;
-            } else if (lds_rows <= 150 * 1024) {
-                // per-row Gauss-Seidel in LDS, writes out_loss directly
-                set_lds(k_loss_rows<K, true>, lds_rows);
-                HIP_CHECK(hipMemsetAsync(&P.flags->changed, 0, 4, st));
-                // host entry: row chunks, each chunk's loss rows sent as soon as it is done
-                pack_pred(0, nloc);
-                const uint32_t nchunk = std::max<uint32_t>(1, std::min<uint32_t>(c.loss_chunks ? c.loss_chunks : sink_rows ? 8 : 1, nloc));
-                for (uint32_t q = 0; q < nchunk; ++q) {
-                    const uint32_t r0 = (uint32_t)((uint64_t)nloc * q / nchunk);
-                    const uint32_t r1 = (uint32_t)((uint64_t)nloc * (q + 1) / nchunk);
-                    if (r1 == r0) continue;
-                    k_loss_rows<K, true><<<r1 - r0, 1024, lds_rows, st>>>(PREDK, Vp, V, lnodes, nloc, ent_ub, ent_w,
-                                                                   DST, npad, cscoff, cscent, P.selfloss, nodes, n,
-                                                                   lpos, out_loss, &P.flags->changed, r0);
-                    HIP_CHECK(hipGetLastError());
-                    if (sink_rows) sink->send_rows(st, out_loss, sink->loss, pl.p0 + r0, r1 - r0, 4);
-                }
-                if (sink_rows) sink->loss_sent = true;
-                rb_async(c, MS_CHANGED, &P.flags->changed, st);
-                HIP_CHECK(hipStreamSynchronize(st));
-                rounds = (int)rb_get<uint32_t>(c, MS_CHANGED);
-                loss_written = true;
-            } else {
-                float* L0 = (float*)c.b_L0.get(nmax * Vp * 4);
-                float* L1 = (float*)c.b_L1.get(nmax * Vp * 4);
-                k_fill<float><<<grid_for((size_t)nloc * Vp), kThreads, 0, st>>>(L0, (size_t)nloc * Vp, 1.0f);
-                float* Lin = L0;
-                float* Lout = L1;
-                for (;;) {
-                    HIP_CHECK(hipMemsetAsync(&P.flags->changed, 0, 4, st));
-                    k_loss_round_sparse<K><<<grid_for((size_t)nloc * V, 256 * 64), kThreads, 0, st>>>(
-                        PRED, Vp, DST, npad, lnodes, nloc, V, ent_ub, ent_w, cscoff, cscent, Lin, Lout,
-                        &P.flags->changed);
-                    HIP_CHECK(hipGetLastError());
-                    ++rounds;
-                    rb_async(c, MS_CHANGED, &P.flags->changed, st);
-                    HIP_CHECK(hipStreamSynchronize(st));
-                    const uint32_t ch = rb_get<uint32_t>(c, MS_CHANGED);
-                    std::swap(Lin, Lout);
-                    if (!ch) break;
-                    if (rounds > (int)V + 2) fail(SRG_ERR_INTERNAL, "loss rounds did not converge");
-                }
-                Lfin = Lin;
-            }
-        }
-    } else {
-        scan_kind = SRG_SCAN_DENSE;
-        if (nloc) {
-            const size_t lds3 = (size_t)2 * KC * (TS + VE) * sizeof(K);
-            set_lds(tight_scan<K, TS, KC>, lds3);
-            tight_scan<K, TS, KC><<<dim3((unsigned)(Vp / TS), (nloc + TS - 1) / TS), 256, lds3, st>>>(D, W, Vp, lnodes,
-                                                                                                    nloc, PRED);
-            k_count_multi<<<nloc, kThreads, 0, st>>>(PRED, nloc, V, Vp, multi_cnt);
-            float* L0 = (float*)c.b_L0.get(nmax * Vp * 4);
-            float* L1 = (float*)c.b_L1.get(nmax * Vp * 4);
-            k_fill<float><<<grid_for((size_t)nloc * Vp), kThreads, 0, st>>>(L0, (size_t)nloc * Vp, 1.0f);
-            HIP_CHECK(hipGetLastError());
-            ms_scan = tm.lap();
-            float* Lin = L0;
-            float* Lout = L1;
-            for (;;) {
-                HIP_CHECK(hipMemsetAsync(&P.flags->changed, 0, 4, st));
-                k_loss_round<K><<<grid_for((size_t)nloc * V, 256 * 64), kThreads, 0, st>>>(
-                    PRED, D, W, WL, lnodes, nloc, V, Vp, Lin, Lout, P.flags);
-                HIP_CHECK(hipGetLastError());
-                ++rounds;
-                rb_async(c, MS_CHANGED, &P.flags->changed, st);
-                HIP_CHECK(hipStreamSynchronize(st));
-                const uint32_t ch = rb_get<uint32_t>(c, MS_CHANGED);
-                std::swap(Lin, Lout);
-                if (!ch) break;
-                if (rounds > (int)V + 2) fail(SRG_ERR_INTERNAL, "loss rounds did not converge");
-            }
-            Lfin = Lin;
-        }
-    }
-    rb_async(c, MS_NMULTI, multi_cnt, st);
-    const double ms_loss = tm.lap();
-    nmulti = rb_get<unsigned long long>(c, MS_NMULTI);
-
-    if (nloc && !loss_written)
-        k_extract<K><<<nloc, kThreads, 0, st>>>(D, Lfin, Vp, lnodes, nloc, nodes, n, lpos,
-                                                                      P.selflat, P.selfloss, out_lat, out_loss,
-                                                                      P.flags, 2, P.unit);
-    HIP_CHECK(hipGetLastError());
-    const double ms_extract = tm.lap();
-
-    // ---- output exchange: every rank ends with all n x n rows ----
-    double ms_exchange = 0;
-    if (exchange) {
-        exchange_rows(out_loss, 4);
-        st_after_cs();
-        ms_exchange = tm.lap();
-    }
-    if (stats) {
-        stats->ms_build += ms_build;
-        stats->ms_fw += ms_fw;
-        stats->ms_scan += ms_scan;
-        stats->ms_loss += ms_loss;
-        stats->ms_extract += ms_extract;
-        stats->ms_exchange += ms_exchange + ms_dx;
-        stats->path_kind = sizeof(K) == 4 ? SRG_PATH_DENSE_U32 : SRG_PATH_DENSE_U64;
-        stats->loss_rounds = rounds;
-        stats->multi_pred_pairs = nmulti;
-        uint64_t own_tiles = 0;  // symmetric FW: this rank's stored tiles ((I + J) mod G == g)
-        for (int I = 0; I < pl.nb; ++I)
-            for (int J = I; J < pl.nb; ++J) own_tiles += (I + J) % pl.G == pl.g;
-        stats->relaxations = sym_fw_for<K, T>(c, g) ? own_tiles * (uint64_t)pl.nb * T * T * T
-                                                    : (uint64_t)(pl.rb1 - pl.rb0) * T * Vp * Vp;
-        stats->essential_edges = n_ess;
-        stats->scan_kind = scan_kind;
-        stats->nranks = pl.G;
-        stats->rank = pl.g;
-        stats->local_sources = nloc;
-    }
-    return true;
-}
-
-// ---- sparse path: batched lexicographic Bellman-Ford (sparse.hip.h) ----------------------
-// Rank r routes the used sources at positions [r*n/G, (r+1)*n/G) (contiguous output rows).
-// Returns false when a used pair came out saturated/unreachable and the graph's latencies
-// could exceed the u32 keys: the caller then reruns on the wide (u64-key) labels.
-bool run_sparse(srg_ctx& c, const DevGraph& g, const uint32_t* nodes, uint32_t n, uint64_t* out_lat,
-                float* out_loss, hipStream_t st, const Prelude& P, srg_stats* stats, bool wide = false) {
-    if (wide && c.kout_key) fail(SRG_INTERNAL_NEED_U64, "the build needs u64 latency keys: no u32 key table");
-    const uint32_t V = g.V;
-    const bool multi = c.comm && c.comm->nranks > 1;
-    const int G = multi ? c.comm->nranks : 1, rk = multi ? c.comm->rank : 0;
-    Timer tm(st);
-    uint32_t* off = (uint32_t*)c.b_indeg.get(((size_t)V + 1) * 4);
-    uint32_t* cur = (uint32_t*)c.b_cscfill.get(((size_t)V + 1) * 4);
-    const uint32_t* esrc = g.src;
-    const uint32_t* edst = g.dst;
-    const uint64_t* selflat = P.selflat;
-    const float* selfloss = P.selfloss;
-    const uint32_t* cols = nodes;
-    // CSR of in-arcs
-    HIP_CHECK(hipMemsetAsync(cur, 0, ((size_t)V + 1) * 4, st));
-    if (g.E) k_csr_count<<<grid_for(g.E), kThreads, 0, st>>>(g.E, esrc, edst, g.directed, cur);
-    size_t tb = 0;
-    HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, cur, off, (int)(V + 1), st));
-    void* tmp = c.b_scantmp.get(tb);
-    HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(tmp, tb, cur, off, (int)(V + 1), st));
-    uint32_t arcs = 0;
-    HIP_CHECK(hipMemcpyAsync(&arcs, off + V, 4, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    uint32_t* in_src = (uint32_t*)c.b_entkey.get(std::max<size_t>(arcs, 1) * 4);
-    uint32_t* in_w = (uint32_t*)c.b_entw.get(std::max<size_t>(arcs, 1) * 4);
-    float* in_b = (float*)c.b_entb.get(std::max<size_t>(arcs, 1) * 4);
-    uint64_t* in_w64 = wide ? (uint64_t*)c.b_cscent.get(std::max<size_t>(arcs, 1) * 8) : nullptr;
-    HIP_CHECK(hipMemsetAsync(cur, 0, ((size_t)V + 1) * 4, st));
-    if (g.E)
-        k_csr_fill<<<grid_for(g.E), kThreads, 0, st>>>(g.E, esrc, edst, g.lat, P.unit, g.loss, g.directed, off, cur,
-                                                       in_src, in_w, in_b, in_w64);
-    // out-arcs for the work marks: the in-CSR itself when undirected
-    const uint32_t* out_off = off;
-    const uint32_t* out_dst = in_src;
-    if (g.directed) {
-        uint32_t* ooff = (uint32_t*)c.b_outoff.get(((size_t)V + 1) * 4);
-        uint32_t* odst = (uint32_t*)c.b_outdst.get(std::max<size_t>(arcs, 1) * 4);
-        HIP_CHECK(hipMemsetAsync(cur, 0, ((size_t)V + 1) * 4, st));
-        k_csr_count_out<<<grid_for(g.E), kThreads, 0, st>>>(g.E, esrc, edst, cur);
-        HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(tmp, tb, cur, ooff, (int)(V + 1), st));
-        HIP_CHECK(hipMemsetAsync(cur, 0, ((size_t)V + 1) * 4, st));
-        k_csr_fill_out<<<grid_for(g.E), kThreads, 0, st>>>(g.E, esrc, edst, ooff, cur, odst);
-        out_off = ooff;
-        out_dst = odst;
-    }
-    // this rank's sources, in graph-locality (BFS) order, in batches of 64 lanes: sources of
-    // one batch are close to each other, so their Bellman-Ford frontiers move together
-    const uint32_t p0 = (uint32_t)((uint64_t)rk * n / G), p1 = (uint32_t)((uint64_t)(rk + 1) * n / G);
-    c.own_row0 = p0;  // this rank's rows: positions [p0, p1) of `nodes`
-    c.own_row1 = p1;
-    const uint32_t nloc = p1 - p0;
-    const uint32_t nbatch = (nloc + 63) / 64;
-    const double ms_csr = std::getenv("SRG_DEBUG_SPARSE") ? tm.lap() : 0.0;  // (debug split of ms_build)
-    const auto t_host0 = std::chrono::steady_clock::now();
-    std::vector<uint32_t> h_off(V + 1), h_src(arcs);
-    HIP_CHECK(hipMemcpyAsync(h_off.data(), off, ((size_t)V + 1) * 4, hipMemcpyDeviceToHost, st));
-    if (arcs) HIP_CHECK(hipMemcpyAsync(h_src.data(), in_src, (size_t)arcs * 4, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    const auto t_host1 = std::chrono::steady_clock::now();
-    std::vector<uint32_t> order(V, 0xFFFFFFFFu), queue;
-    queue.reserve(V);
-    uint32_t next = 0;
-    for (uint32_t root_pass = 0; root_pass < 2 && next < V; ++root_pass) {
-        for (uint32_t r = 0; r < V; ++r) {
-            // first pass: start at the highest-degree vertex; then any unvisited vertex
-            uint32_t start = r;
-            if (root_pass == 0) {
-                uint32_t best = 0;
-                for (uint32_t v = 0; v < V; ++v)
-                    if (h_off[v + 1] - h_off[v] > h_off[best + 1] - h_off[best]) best = v;
-                start = best;
-            }
-            if (order[start] != 0xFFFFFFFFu) continue;
-            order[start] = next++;
-            queue.assign(1, start);
-            for (size_t qi = 0; qi < queue.size(); ++qi) {
-                const uint32_t v = queue[qi];
-                for (uint32_t k = h_off[v]; k < h_off[v + 1]; ++k) {
-                    const uint32_t u = h_src[k];
-                    if (order[u] == 0xFFFFFFFFu) {
-                        order[u] = next++;
-                        queue.push_back(u);
-                    }
-                }
-            }
-            if (root_pass == 0) break;
-        }
-    }
-    const auto t_host2 = std::chrono::steady_clock::now();
-    std::vector<uint32_t> loc(nloc);
-    for (uint32_t i = 0; i < nloc; ++i) loc[i] = p0 + i;
-    if (c.sparse_locality) {  // stable by BFS position: a counting sort over the V positions
-        std::vector<uint32_t> cnt((size_t)V + 1, 0);
-        for (uint32_t i = 0; i < nloc; ++i) ++cnt[order[P.nodes_h[p0 + i]] + 1];
-        for (uint32_t v = 0; v < V; ++v) cnt[v + 1] += cnt[v];
-        for (uint32_t i = 0; i < nloc; ++i) loc[cnt[order[P.nodes_h[p0 + i]]]++] = p0 + i;
-    }
-    std::vector<uint32_t> bsrc((size_t)std::max<uint32_t>(nbatch, 1) * 64), brow(bsrc.size());
-    for (uint32_t i = 0; i < (uint32_t)bsrc.size(); ++i) {
-        const bool real = i < nloc;
-        bsrc[i] = P.nodes_h[real ? loc[i] : (nloc ? loc[0] : 0)];
-        brow[i] = real ? loc[i] : 0xFFFFFFFFu;
-    }
-    const auto t_host3 = std::chrono::steady_clock::now();
-    uint32_t* d_bsrc = (uint32_t*)c.b_lnodes.get(bsrc.size() * 4);
-    uint32_t* d_brow = (uint32_t*)c.b_lpos.get(brow.size() * 4);
-    HIP_CHECK(hipMemcpyAsync(d_bsrc, bsrc.data(), bsrc.size() * 4, hipMemcpyHostToDevice, st));
-    HIP_CHECK(hipMemcpyAsync(d_brow, brow.data(), brow.size() * 4, hipMemcpyHostToDevice, st));
-    uint32_t* fl = (uint32_t*)c.b_red.get(128);
-    HIP_CHECK(hipMemsetAsync(fl, 0, 128, st));
-    HIP_CHECK(hipGetLastError());
-    const double ms_build = tm.lap() + ms_csr;
-    if (std::getenv("SRG_DEBUG_SPARSE"))
-        std::fprintf(stderr, "sparse build: CSR %.2f ms, host order + batches %.2f ms (of %.2f): CSR to host %.2f, BFS %.2f, batches %.2f\n", ms_csr,
-                     std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_host0).count(), ms_build,
-                     std::chrono::duration<double, std::milli>(t_host1 - t_host0).count(),
-                     std::chrono::duration<double, std::milli>(t_host2 - t_host1).count(),
-                     std::chrono::duration<double, std::milli>(t_host3 - t_host2).count());
-
-    int dev_cus = 256;
-    HIP_CHECK(hipDeviceGetAttribute(&dev_cus, hipDeviceAttributeMultiprocessorCount, c.device));
-    // wide labels take the 128-VGPR budget: one workgroup per CU
-    const int wpc = wide ? 1 : 2;
-    uint32_t grid = std::max<uint32_t>(1, std::min<uint32_t>(nbatch, (uint32_t)dev_cus * (uint32_t)wpc));
-
-    // u32 latency keys take the two-phase kernel (latency-only delta-stepping, then the loss fold
-    // over the tight arcs, sparse_ds.hip.h); wide labels keep the lexicographic sweeps.
-    // SRG_SPARSE_KERNEL=bf selects the lexicographic sweeps for u32 keys too (A/B)
-    const char* sk = std::getenv("SRG_SPARSE_KERNEL");
-    const bool two_phase = !wide && !(sk && std::strcmp(sk, "bf") == 0);
-    // per resident batch: labels V x 64 x 8 B (16 B wide); two-phase: u32 latency + f32 loss
-    // labels, a u64 tight mask per arc and a u64 final-lane mask per vertex
-    size_t free_b = 0, total_b = 0;
-    HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
-    const size_t slot_bytes = (size_t)V * 64 * (wide ? 16 : two_phase ? 4 : 8);
-    const size_t ds_extra = two_phase ? (size_t)V * 64 * 4 + (size_t)std::max<uint32_t>(arcs, 1) * 16 + (size_t)V * 16 : 0;
-    // two launches (phase 1, then phases 2 + output) when every batch's latency labels fit beside the
-    // rest (C4: 782 x 12.8 MB = 10 GB): each launch gets its own register allocation
-    // (SRG_SPARSE_SPLIT=0: one fused launch, A/B)
-    const char* sp_env = std::getenv("SRG_SPARSE_SPLIT");
-    const size_t d_all = (size_t)nbatch * V * 64 * 4;
-    const bool split = two_phase && nbatch && !(sp_env && sp_env[0] == '0') && d_all <= free_b / 3;
-    grid = (uint32_t)std::max<size_t>(
-        1, std::min<size_t>(grid, (free_b / 2 - (split ? d_all : 0)) / std::max<size_t>((split ? 0 : slot_bytes) + ds_extra, 1)));
-    const uint32_t nwv = (V + 63) / 64;
-    const size_t bitmap_bytes = two_phase ? ds_state_bytes(V) : (size_t)nwv * 5 * 8;
-    const size_t scr_bytes = two_phase ? ds_scratch_bytes() : sp_scratch_bytes();
-    // bitmaps in LDS while a CU still fits the requested workgroups, else in global memory
-    const bool gbits = c.sparse_global_bitmaps || bitmap_bytes + scr_bytes > (size_t)160 * 1024 / wpc;
-    const size_t lds = (gbits ? 0 : bitmap_bytes) + scr_bytes;
-    if (nbatch) {
-        unsigned long long* slots = (unsigned long long*)c.b_D.get(split ? d_all : (size_t)grid * slot_bytes);
-        unsigned long long* gb = gbits ? (unsigned long long*)c.b_W.get((size_t)grid * bitmap_bytes) : nullptr;
-        // 16 rows in flight was measured 2.5x slower (the row array no longer unrolls into
-        // registers); 4 ties with 8 at 2 workgroups per CU
-        // 8 rows in flight at two workgroups per CU: 4 rows tied, 16 rows / one workgroup per CU
-        // (128 VGPRs, no spills) ran 2.5x / 1.2x slower
-        auto kern = gbits ? k_sparse_bf<SP_G, true> : k_sparse_bf<SP_G, false>;
-        if (wide) kern = gbits ? k_sparse_bf<SP_G, true, 4, LabelU64> : k_sparse_bf<SP_G, false, 4, LabelU64>;
-        if (two_phase) {
-            // 8 rows in flight per wave: 16 and 32 spill at the 64-VGPR budget and measured 375 / 712 ms
-            // against 293 on C4 (profiles/r06/sparse_ds/c4_g*.json)
-            kern = gbits ? k_sparse_ds<true, 8, 8> : k_sparse_ds<false, 8, 8>;
-        }
-        set_lds(kern, lds);
-        SparseArgs a{off, in_src, in_w, in_b, out_off, out_dst, V, d_bsrc, d_brow, nbatch, slots, fl + 4, cols, n,
-                     selflat, selfloss, out_lat, out_loss, fl, P.unit, ~0ull, gb, c.kout_key, c.kout_diag,
-                     in_w64, min_edge_key(P.es.min_lat_inv, P.unit), nullptr, nullptr, nullptr, arcs};
-        if (two_phase) {
-            a.lo_slots = (float*)c.b_WL.get((size_t)grid * V * 64 * 4);
-            // tight records (16 B per in-arc slot), final-lane masks + tight-record counts (16 B per vertex)
-            a.tmask = (unsigned long long*)c.b_PRED.get((size_t)grid * std::max<uint32_t>(arcs, 1) * 16);
-            a.fmask = (unsigned long long*)c.b_L0.get((size_t)grid * V * 16);
-        }
-        // bucket width: the largest edge latency / sparse_delta_div (0 = one bucket, plain BF)
-        if (c.sparse_delta_div > 0)
-            a.delta = std::max<unsigned long long>(1ull, P.max_key / (unsigned long long)c.sparse_delta_div);
-        const char* dbg_env = std::getenv("SRG_DEBUG_SPARSE");
-        const bool dbg_batches = two_phase && dbg_env && dbg_env[0] == '2';
-        if (dbg_batches) {
-            a.dbg = (uint32_t*)c.b_L1.get((size_t)nbatch * 6 * 4);
-            HIP_CHECK(hipMemsetAsync(a.dbg, 0, (size_t)nbatch * 6 * 4, st));
-        }
-        if (c.profiling) {
-            while (c.prof_events.size() < 2) {
-                hipEvent_t e;
-                HIP_CHECK(hipEventCreate(&e));
-                c.prof_events.push_back(e);
-            }
-            HIP_CHECK(hipEventRecord(c.prof_events[0], st));
-        }
-        if (split) {
-            auto k1 = gbits ? k_sparse_ds<true, 8, 8, 1> : k_sparse_ds<false, 8, 8, 1>;
-            auto k2 = gbits ? k_sparse_ds<true, 8, 8, 2> : k_sparse_ds<false, 8, 8, 2>;
-            // (phase 1 in 8-wave workgroups at 128 VGPRs with 32 rows in flight per wave, no spills, was
-            // measured slower: 151 vs 115 ms per workgroup, profiles/r06/sparse_p1w/)
-            set_lds(k1, lds);
-            set_lds(k2, lds);
-            k1<<<grid, SP_THREADS, lds, st>>>(a);
-            SparseArgs a2 = a;
-            a2.queue = fl + 9;  // (zeroed with the flags)
-            k2<<<grid, SP_THREADS, lds, st>>>(a2);
-        } else {
-            kern<<<grid, SP_THREADS, lds, st>>>(a);
-        }
-        HIP_CHECK(hipGetLastError());
-        if (c.profiling) HIP_CHECK(hipEventRecord(c.prof_events[1], st));
-        if (dbg_batches) {  // per-batch durations (100-MHz ticks): what sets the launches' makespan
-            std::vector<uint32_t> h((size_t)nbatch * 6);
-            HIP_CHECK(hipMemcpyAsync(h.data(), a.dbg, h.size() * 4, hipMemcpyDeviceToHost, st));
-            HIP_CHECK(hipStreamSynchronize(st));
-            for (int ph = 0; ph < 2; ++ph) {
-                std::vector<double> d(nbatch);
-                for (uint32_t b = 0; b < nbatch; ++b) {
-                    d[b] = h[b * 6 + 1 + 4 * ph] / 1e5;
-                }
-                std::vector<double> srt = d;
-                std::sort(srt.begin(), srt.end());
-                std::fprintf(stderr, "sparse batches phase %d (ms): min %.1f p10 %.1f median %.1f p90 %.1f max %.1f; by batch decile:",
-                             ph + 1, srt[0], srt[nbatch / 10], srt[nbatch / 2], srt[nbatch * 9 / 10], srt[nbatch - 1]);
-                for (int q = 0; q < 10; ++q) {
-                    double m = 0;
-                    uint32_t cnt = 0;
-                    for (uint32_t b = q * nbatch / 10; b < (q + 1) * nbatch / 10; ++b) m += d[b], ++cnt;
-                    std::fprintf(stderr, " %.1f", cnt ? m / cnt : 0.0);
-                }
-                std::fprintf(stderr, "\n");
-            }
-            std::fprintf(stderr, "sparse batches phase-1 sweeps:");
-            for (uint32_t b = 0; b < nbatch; b += std::max<uint32_t>(1, nbatch / 20)) std::fprintf(stderr, " %u", h[b * 6 + 3]);
-            std::fprintf(stderr, "\n");
-        }
-    }
-    // every rank agrees on the outcome before any exchange
-    if (multi) {
-        c.comm->allreduce_max_u32(fl, 2, st);
-        c.comm->allreduce_max_u32(fl + 5, 3, st);  // saturated, impossible, fold incomplete
-    }
-    uint32_t hfl[26] = {};
-    HIP_CHECK(hipMemcpyAsync(hfl, fl, 104, hipMemcpyDeviceToHost, st));
-    const double ms_sssp = tm.lap();
-    if (hfl[7])
-        fail(SRG_ERR_INTERNAL, "the sparse build's loss fold left a used pair without a final loss");
-    if (hfl[6])
-        fail(SRG_ERR_INTERNAL, "the sparse build produced an impossible table: a used pair's latency is below the "
-                               "smallest edge latency (" + std::to_string(~P.es.min_lat_inv) + " ns)");
-    if (std::getenv("SRG_DEBUG_SPARSE")) {
-        const unsigned long long ev = (unsigned long long)hfl[2] | (unsigned long long)hfl[3] << 32;
-        const unsigned long long p2 = (unsigned long long)hfl[10] | (unsigned long long)hfl[11] << 32;
-        std::fprintf(stderr,
-                     "sparse: %s, %u batches, grid %u, max sweeps %u, lane evaluations %llu, fold sweeps %u, "
-                     "fold row pulls %llu, arcs %u\n",
-                     two_phase ? "two-phase" : "lexicographic", nbatch, grid, hfl[1], ev, hfl[8], p2, arcs);
-        if (two_phase) {  // per-phase wall clock summed over workgroups (100 MHz), as ms per workgroup
-            double t[4];
-            for (int p = 0; p < 4; ++p)
-                t[p] = (double)((unsigned long long)hfl[12 + 2 * p] | (unsigned long long)hfl[13 + 2 * p] << 32) / 1e5 / grid;
-            std::fprintf(stderr, "sparse phases (ms per workgroup): latency %.1f, tight masks %.1f, fold %.1f, output %.1f\n",
-                         t[0], t[1], t[2], t[3]);
-            double b[3];  // wave utilisation: ticks inside window visits / (16 waves x the phase's ticks)
-            for (int p = 0; p < 3; ++p)
-                b[p] = (double)((unsigned long long)hfl[20 + 2 * p] | (unsigned long long)hfl[21 + 2 * p] << 32) / 1e5 / grid /
-                       (16.0 * std::max(t[p], 1e-9));
-            std::fprintf(stderr, "sparse wave utilisation: latency %.2f, tight masks %.2f, fold %.2f\n", b[0], b[1], b[2]);
-        }
-    }
-    if (hfl[0]) {
-        // a used pair came out INF: only a relaxation that saturated the u32 key can have hidden a
-        // finite (>= 2^32-1 ns) path; otherwise the pair is unreachable -- the reference's panic
-        if (hfl[5] && !wide) return false;  // rerun on the wide labels
-        fail(SRG_ERR_UNREACHABLE,
-             "assertion `left == right` failed: paths.len() != nodes.len().pow(2) (a used node is unreachable "
-             "from another used node)");
-    }
-    double ms_exchange = 0;
-    if (multi && c.gather_output) {
-        std::vector<size_t> offs(G), lens(G);
-        for (int elem : {8, 4}) {
-            for (int r = 0; r < G; ++r) {
-                const size_t a0 = (uint64_t)r * n / G, a1 = (uint64_t)(r + 1) * n / G;
-                offs[r] = a0 * n * elem;
-                lens[r] = (a1 - a0) * n * elem;
-            }
-            c.comm->allgatherv(elem == 8 ? (void*)out_lat : (void*)out_loss, offs.data(), lens.data(), st);
-        }
-        ms_exchange = tm.lap();
-    }
-    if (stats && c.profiling && nbatch) {
-        float ms = 0;
-        HIP_CHECK(hipEventElapsedTime(&ms, c.prof_events[0], c.prof_events[1]));
-        stats->prof_launches += 1;
-        stats->prof_kernel_ms += ms;
-        stats->prof_relaxations += nloc;  // sparse: sources routed by the profiled launch
-    }
-    if (stats) {
-        stats->ms_build += ms_build;
-        stats->ms_fw += ms_sssp;
-        stats->ms_exchange += ms_exchange;
-        stats->path_kind = wide ? SRG_PATH_SPARSE_U64 : SRG_PATH_SPARSE_U32;
-        stats->loss_rounds = (int)hfl[1];
-        stats->relaxations = (((uint64_t)hfl[3] << 32) | hfl[2]) * 64;
-        stats->nranks = G;
-        stats->rank = rk;
-        stats->local_sources = nloc;
-    }
-    return true;
-}
-
-bool choose_sparse(const srg_ctx& c, const DevGraph& g) {
-    if (c.algorithm == SRG_ALGO_DENSE) return false;
-    if (c.algorithm == SRG_ALGO_SPARSE) return true;
-    const double arcs = (double)g.E * (g.directed ? 1.0 : 2.0);
-    return g.V >= 2048 && arcs * 32.0 < (double)g.V * g.V;
-}
+#include "dense.hip.h"
+#include "sparse_run.hip.h"
 
 void compute_device(srg_ctx& c, const DevGraph& g, const uint32_t* nodes, uint32_t n, uint64_t* out_lat,
                     float* out_loss, hipStream_t st, srg_stats* stats, HostSink* sink = nullptr,
@@ -3163,8 +2169,7 @@ void compute_device(srg_ctx& c, const DevGraph& g, const uint32_t* nodes, uint32
     // latency unit: every non-self-loop latency is a multiple of their gcd, hence so is every path
     // sum; keys count units (a ms-granular graph fits u32 keys up to 2^31-1 ms of path), outputs
     // are key * unit -- exact.  SRG_LATENCY_UNIT=1 keeps nanosecond keys (tests, A/B).
-    const char* lu = std::getenv("SRG_LATENCY_UNIT");
-    const uint64_t unit = (P.es.unit > 1 && !(lu && std::strcmp(lu, "1") == 0)) ? P.es.unit : 1;
+    const uint64_t unit = (P.es.unit > 1 && !srg_env::latency_unit_ns()) ? P.es.unit : 1;
     P.unit = unit;
     // the FW that ran beside the H2D counted nanoseconds (exact for any unit; its certification
     // decides as usual, a failure reruns on the u64 keys)
@@ -3435,7 +2440,7 @@ void ensure_pool(srg_ctx& c) {
     c.pool = new HostPool();
     const unsigned hw = std::thread::hardware_concurrency();
     int nt = (int)std::max(1u, std::min(8u, hw ? hw : 1u));
-    if (const char* e = std::getenv("SRG_CODEC_THREADS")) nt = std::max(1, std::atoi(e));  // experiments
+    if (const int e = srg_env::codec_threads()) nt = e;  // experiments
     c.pool->start(nt);
 }
 void ensure_rings(srg_ctx& c) {
@@ -3447,11 +2452,9 @@ void ensure_rings(srg_ctx& c) {
         HIP_CHECK(hipHostMalloc(&c.h_ring, slot * kRingSlots, hipHostMallocDefault));
         c.h_ring_bytes = slot * kRingSlots;
     }
-    for (hipEvent_t& e : c.ev_ring)
-        if (!e) HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    for (Event& e : c.ev_ring) e.create();
     if (!c.h_lring) HIP_CHECK(hipHostMalloc(&c.h_lring, kCodecChunk * 4 * kRingSlots, hipHostMallocDefault));
-    for (hipEvent_t* e : {&c.ev_lring[0], &c.ev_lring[1], &c.ev_lring[2], &c.ev_lin, &c.ev_ldone})
-        if (!*e) HIP_CHECK(hipEventCreateWithFlags(e, hipEventDisableTiming));
+    for (Event* e : {&c.ev_lring[0], &c.ev_lring[1], &c.ev_lring[2], &c.ev_lin, &c.ev_ldone}) e->create();
 }
 
 bool codec_in(srg_ctx& c, const srg_edge_list* g, DevGraph& dg, hipStream_t st, size_t a0, size_t a1, bool with_loss,
@@ -3476,11 +2479,10 @@ bool codec_in(srg_ctx& c, const srg_edge_list* g, DevGraph& dg, hipStream_t st, 
     const double ms_setup = ms_since(t_setup);  // (first call: worker threads, pinned ring, device arrays)
     std::atomic<bool> bad{false};     // a latency >= 2^32: the codec cannot carry the list
     std::atomic<bool> bad_ep{false};  // an endpoint >= 65536: only the sequential-pair chunks can
-    const bool dbg = std::getenv("SRG_DEBUG_CODEC") != nullptr;
+    const bool dbg = srg_env::debug_codec();
     double t_conv = 0, t_wait = 0;
     const size_t nch = (A + CE - 1) / CE;
-    const char* sq = std::getenv("SRG_CODEC_SEQ");
-    bool seq = !(sq && std::strcmp(sq, "0") == 0);  // (a slice of a row-ordered list is row-ordered too)
+    bool seq = !srg_env::codec_seq_off();  // (a slice of a row-ordered list is row-ordered too)
     uint32_t* dexc = seq ? (uint32_t*)c.b_exc.get(CE * 4) : nullptr;
     const int nwk = c.pool->size();
     if ((int)c.codec_ex.size() < nwk) c.codec_ex.resize(nwk);
@@ -3555,7 +2557,7 @@ bool codec_in(srg_ctx& c, const srg_edge_list* g, DevGraph& dg, hipStream_t st, 
         // faulted in beside it (0.79 ms against 0.76) switched a C3 first call over (round 6)
         const double plain_ms = (double)ne * 20.0 / 55e9 * 1e3;
         bool slow = ch + 1 < nch && ch >= 1 && t_conv / (double)(ch + 1) > 1.5 * plain_ms;
-        if (const char* f = std::getenv("SRG_CODEC_SLOW_AFTER")) slow = ch + 1 < nch && ch >= (size_t)std::atoll(f);  // tests
+        if (size_t k = 0; srg_env::codec_slow_after(k)) slow = ch + 1 < nch && ch >= k;  // tests
         if (chunk_seq) {
             // the workers' exception lists, in order, as SoA (index | src | dst) where the u16
             // endpoints would have gone
@@ -3633,7 +2635,7 @@ void start_late_loss(srg_ctx& c, const srg_edge_list* g, DevGraph& dg, hipStream
         constexpr int NB = 3;
         try {
             HIP_CHECK(hipSetDevice(device));
-            const bool dbg = std::getenv("SRG_DEBUG_OVERLAP") != nullptr;
+            const bool dbg = srg_env::debug_overlap();
             const auto t0 = std::chrono::steady_clock::now();
             double t_copy = 0, t_wait = 0;
             const size_t E = std::min<size_t>(g->num_edges, a1);  // this rank's slice [a0, E)
@@ -3758,7 +2760,7 @@ int host_entry(srg_ctx* c, const srg_edge_list* g, const uint32_t* nodes, uint32
     } reg;
     reg.device = c->device;
     reg.wait = c->d2h_stream;
-    if (const char* e = std::getenv("SRG_PREFAULT")) reg.fault = std::strcmp(e, "0") != 0;  // A/B
+    reg.fault = srg_env::prefault_on();  // A/B
     const bool early = !direct && nn * 12 >= ((size_t)64 << 20);
     const bool ext = (bool)c->ext_reg;
     // a rank of a group that fills only its own rows [n r / N, n (r+1) / N) of a table the ranks
@@ -3832,7 +2834,7 @@ int host_entry(srg_ctx* c, const srg_edge_list* g, const uint32_t* nodes, uint32
         const int ov_early = ov.next;  // pivots enqueued while chunks were still crossing
         if (stats && ov.on && ov.ok) stats->fw_overlap_pivots = ov_early;
         if (ov.on && ov.ok && !ov.ended) ov.advance(ov.nb - 1);
-        if (ov.on && std::getenv("SRG_DEBUG_OVERLAP")) {
+        if (ov.on && srg_env::debug_overlap()) {
             std::fprintf(stderr, "fw-overlap: ok=%d pivots_during_h2d=%d of %d\n", ov.ok ? 1 : 0, ov_early, ov.nb);
             if (ov.ok) ov.report();
         }
@@ -3997,7 +2999,7 @@ int host_entry(srg_ctx* c, const srg_edge_list* g, const uint32_t* nodes, uint32
         // keys and are widened on the host (HostSink::send_keys; 0.6 GB less D2H at C3); a build that
         // turns out to need u64 keys ships the u64 rows instead (run_dense clears sink.widen)
         bool ikeys = !keys && !direct && early && nr == 1 && c->sdma.ok && c->d2h_mode == 1 && c->h_ring &&
-                     c->pool && (size_t)n * 4 <= c->h_ring_bytes / 3 && !std::getenv("SRG_NO_KEY_D2H");
+                     c->pool && (size_t)n * 4 <= c->h_ring_bytes / 3 && !srg_env::no_key_d2h();
         {
             DevGraph probe{g->num_vertices, (int)g->directed, E};
             ikeys = ikeys && !choose_sparse(*c, probe);
@@ -4165,7 +3167,7 @@ int srg_create(srg_ctx** out, int device, char* errbuf, size_t errlen) {
     srg_ctx* c = nullptr;
     int rc = guard(errbuf, errlen, [&]() {
         // SRG_DEBUG_CREATE: where srg_create's time goes (the cold call Shadow pays once)
-        const bool dbg = std::getenv("SRG_DEBUG_CREATE") != nullptr;
+        const bool dbg = srg_env::debug_create();
         auto tc = std::chrono::steady_clock::now();
         auto lap = [&](const char* what) {
             if (dbg) std::fprintf(stderr, "srg_create: %-28s %7.2f ms\n", what, ms_since(tc));
@@ -4207,9 +3209,9 @@ int srg_create(srg_ctx** out, int device, char* errbuf, size_t errlen) {
         // stream would share a hardware queue (GPU_MAX_HW_QUEUES = 4) with the main stream and
         // serialise the W build and FW behind the loss DMAs (measured: build 1.0 -> 3.6 ms)
         c->loss_stream = c->d2h_stream;
-        for (hipEvent_t* e : {&c->ev_a, &c->ev_b, &c->ev_c, &c->ev_d, &c->ev_e, &c->ev_ledges, &c->ev_wlate, &c->ev_fwreset,
-                              &c->ev_dst})
-            HIP_CHECK(hipEventCreateWithFlags(e, hipEventDisableTiming));
+        for (Event* e : {&c->ev_a, &c->ev_b, &c->ev_c, &c->ev_d, &c->ev_e, &c->ev_ledges, &c->ev_wlate, &c->ev_fwreset,
+                         &c->ev_dst})
+            e->create();
         int wv = 0;
         if (hipDeviceGetAttribute(&wv, hipDeviceAttributeCanUseStreamWaitValue, device) == hipSuccess && wv) {
             for (uint32_t*& p : c->sig) HIP_CHECK(hipExtMallocWithFlags((void**)&p, 8, hipMallocSignalMemory));
@@ -4218,8 +3220,7 @@ int srg_create(srg_ctx** out, int device, char* errbuf, size_t errlen) {
             HIP_CHECK(hipStreamSynchronize(c->stream));
         }
         lap("events, signals");
-        const char* wv_env = std::getenv("SRG_CREATE_WARM");
-        if (!(wv_env && wv_env[0] == '0')) {
+        if (!srg_env::create_warm_off()) {
             warm_context(*c);
             lap("warm-up (module, rings, copies)");
         }

@@ -28,7 +28,7 @@ def share_unique_id(group=None, make_id=None):
 
 
 def split_rows(num_blocks, nranks):
-    """Row blocks of the general (non-symmetric) FW: [r*nb//G, (r+1)*nb//G) (routing.hip make_plan)."""
+    """Row blocks of the general (non-symmetric) FW: [r*nb//G, (r+1)*nb//G) (plan.h make_plan)."""
     return [(r * num_blocks // nranks, (r + 1) * num_blocks // nranks) for r in range(nranks)]
 
 

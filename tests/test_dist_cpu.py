@@ -1,7 +1,7 @@
 """CPU, world_size 2 over gloo: the torch.distributed bring-up of the multi-GPU path
 (shadow_amd/dist.py) and bench.py's timing protocol (barrier, max over ranks).  The RCCL
 unique id is created by the native library on rank 0 (no GPU needed for that) and must reach
-every rank intact; the row-block split must be the library's (routing.hip make_plan); and the
+every rank intact; the row-block split must be the library's (plan.h make_plan); and the
 distributed FW schedule itself (shadow_amd.dist.line_fw) runs on 2-4 gloo ranks."""
 import os
 import socket

@@ -1,4 +1,4 @@
-"""The symmetric FW bulk launched in XCD Z-order runs (SRG_OPT_FW_XCD_ORDER = 1, routing.hip
+"""The symmetric FW bulk launched in XCD Z-order runs (SRG_OPT_FW_XCD_ORDER = 1, plan.h
 xcd_tile_order) computes the same closure as triangle order: bit-identical tables through the host
 entry (with and without the FW beside the H2D).  Also: a simulated rank (SRG_OPT_SIMULATE_RANK, a
 timing aid whose table is not a result: no peer data) runs to the end -- the impossible-table guard
