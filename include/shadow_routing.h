@@ -176,7 +176,8 @@ void srg_destroy(srg_ctx* ctx);
                                      * entry ships rows early, else 1 */
 #define SRG_OPT_SCAN_GROUPS 22       /* host entry: source-block groups the tight scan is
                                      * launched in, each group's loss rows folded and shipped while
-                                     * later groups scan; 0 (default) = 3, 1 = scan, then loss */
+                                     * later groups scan; 0 (default) = 3 (4 when the scan is mirrored,
+                                     * SRG_OPT_SCAN_MIRROR), 1 = scan, then loss */
 #define SRG_OPT_H2D_CODEC 25         /* host entry: 1 (default) = the edge list crosses PCIe narrowed (u16
                                      * endpoints, u32 latencies; 12 instead of 20 B per edge) when every
                                      * endpoint < 65536 and latency < 2^32, widened on the device; 0 = plain */
@@ -229,6 +230,16 @@ void srg_destroy(srg_ctx* ctx);
                                      * Z-order runs, one list per pivot (each XCD a compact block of the triangle,
                                      * its line-buffer operands L2-resident: C3 bulk HBM traffic 1.38x -> 1.12x of
                                      * the C tiles); 0 = triangle order (consecutive tiles round-robin) */
+#define SRG_OPT_SCAN_MIRROR 40       /* dense build, sparse tight scan: 1 (default) = on an undirected graph whose
+                                     * used nodes are all vertices in order (one rank, u32 keys) scan only the
+                                     * (source block, target tile) pairs on and above the diagonal and derive
+                                     * the pairs below it from them; 0 = scan every pair.  Every
+                                     * other build scans every pair */
+#define SRG_OPT_SCAN_MIRRORED 41     /* read-only: the last build's scan: 0 = every pair scanned, 1 = mirrored,
+                                     * 2 = mirrored, then scanned again in full (its worklist overflowed) */
+#define SRG_OPT_SCAN_MIRROR_CAP 42   /* pairs the mirror's exact-key worklist holds per launch; 0 (default) =
+                                     * 1 / 1024 of the launch's pairs (at least 256); at most what the packed
+                                     * predecessor rows leave free (half the launch's pairs) */
 int srg_set_option(srg_ctx* ctx, int option, double value);
 /* current value of an option (SRG_OK), or SRG_ERR_ARG for an unknown option */
 int srg_get_option(srg_ctx* ctx, int option, double* value);

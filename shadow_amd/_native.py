@@ -54,6 +54,9 @@ SRG_OPT_TABLE_POOL_IDLE_BYTES = 36
 SRG_OPT_CREATE_MS_RUNTIME = 37
 SRG_OPT_CREATE_MS_LIBRARY = 38
 SRG_OPT_FW_XCD_ORDER = 39
+SRG_OPT_SCAN_MIRROR = 40
+SRG_OPT_SCAN_MIRRORED = 41
+SRG_OPT_SCAN_MIRROR_CAP = 42
 SRG_ALGO_AUTO = 0
 SRG_ALGO_DENSE = 1
 SRG_ALGO_SPARSE = 2

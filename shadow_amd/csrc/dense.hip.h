@@ -174,7 +174,8 @@ bool run_dense(srg_ctx& c, const DevGraph& g, const Plan& pl, const uint32_t* no
     constexpr int VE = 16 / (int)sizeof(K);
     const size_t nmax = std::max<uint32_t>(nloc, 1);
     uint32_t* PRED = (uint32_t*)c.b_PRED.get(nmax * Vp * 4);
-    unsigned long long* multi_cnt = (unsigned long long*)c.b_multi.get(8);
+    unsigned long long* multi_cnt = (unsigned long long*)c.b_multi.get(16);
+    uint32_t* mirror_cnt = (uint32_t*)(multi_cnt + 1);  // k_pred_mirror's worklist: {pairs wanted, overflow}
     int rounds = 0;
     unsigned long long nmulti = 0;
     uint64_t n_ess = 0;
@@ -371,57 +372,109 @@ bool run_dense(srg_ctx& c, const DevGraph& g, const Plan& pl, const uint32_t* no
                                                                                   ent_ub, cscent);
         }
         HIP_CHECK(hipGetLastError());
-        // host entry, one rank, per-row LDS loss: scan groups interleaved with the loss rows
         const size_t lds_rows = loss_rows_lds(V);
-        const uint32_t scan_groups = c.scan_groups ? (uint32_t)c.scan_groups : 3u;
+        // Triangular scan (SRG_OPT_SCAN_MIRROR): on an undirected graph whose rows are
+        // the vertices in order, one rank, u32 keys, per-row LDS loss, tight_v5 scans only the pairs
+        // (source block c, target tile b >= c) and k_pred_mirror derives the packed entries below
+        // the diagonal.  Every other build scans every pair.
+        bool mirror = c.scan_mirror && !g.directed && pl.G == 1 && !multi && !simulated && nloc == n && P.ident &&
+                      !v5lo && lds_rows <= 150 * 1024;
+        // host entry, one rank, per-row LDS loss: scan groups interleaved with the loss rows (mirrored:
+        // one group more, the later groups scan little and their rows keep the link fed: C3 host entry
+        // 3 / 4 / 5 groups 44.3 / 43.0 / 42.7 ms, profiles/r07/scan_mirror)
+        const uint32_t scan_groups = c.scan_groups ? (uint32_t)c.scan_groups : mirror ? 4u : 3u;
         const bool interleave = sink_rows && lds_rows <= 150 * 1024 && scan_groups > 1;
-        if (interleave) {
-            set_lds(k_loss_rows<K, true>, lds_rows);
-            HIP_CHECK(hipMemsetAsync(&P.flags->changed, 0, 4, st));
-        }
+        if (interleave) set_lds(k_loss_rows<K, true>, lds_rows);
         // the per-row LDS loss pass reads PRED packed with each single predecessor's {u, 1 - loss}
         // (k_pred_pack, after each scan group); the global-memory fold the entry indices
         uint32_t* PREDK = lds_rows <= 150 * 1024 ? (uint32_t*)c.b_PRED2.get(nmax * Vp * 8) : nullptr;
         auto pack_pred = [&](uint32_t r0, uint32_t r1) {
             const uint32_t nsb = (r1 - r0 + 127) / 128, nt8 = (nbTT5 + 7) / 8;
             k_pred_pack<<<8u * nt8 * nsb, 256, 0, st>>>(PRED, Vp, r0, r1, NT, nbTT5, nsb, ent_ub, (uint2*)PREDK,
-                                                        multi_cnt);
+                                                        multi_cnt, mirror ? 1u : 0u);
             HIP_CHECK(hipGetLastError());
         };
-        if (nloc) {
-            HIP_CHECK(hipStreamWaitEvent(st, c.ev_dst, 0));  // (the scan's DST, built on the aux stream)
+        // the pairs below the diagonal of the rows [r0, r1), after pack_pred(r0, r1) (r0 on a block
+        // bound; the rows before r0 are packed and mirrored).  The worklist of the pairs that need
+        // the exact keys lies in the PRED rows [r0, r1), which are dead once packed (room for half
+        // of all the rows' pairs).  A worklist pair costs a wave that gathers the whole CSC list of
+        // its column, about what the scan spends on a thousand pairs, so the capacity is 1 / 1024 of
+        // the rows' pairs (at least 256): the slow launch stays a small fraction of the scan.  A pair
+        // that does not fit raises mirror_cnt[1]; the mirror kernels then return at once and the
+        // whole scan stage runs again without mirroring (below).
+        auto mirror_rows = [&](uint32_t r0, uint32_t r1) {
+            if (r1 <= r0 || r1 <= SB) return;  // rows of the first block only: nothing below the diagonal
+            const size_t pairs = (size_t)(r1 - r0) * Vp, room = std::min<size_t>(pairs / 2, (size_t)1 << 30);
+            const uint32_t cap = (uint32_t)std::min<size_t>(
+                room, c.scan_mirror_cap ? (size_t)c.scan_mirror_cap : std::max<size_t>(pairs / 1024, 256));
+            uint2* work = (uint2*)(PRED + (size_t)r0 * Vp);
+            HIP_CHECK(hipMemsetAsync(mirror_cnt, 0, 4, st));
+            const uint32_t nlow = (r1 - 1) / SB * SB;  // columns below the last row's diagonal block
+            k_pred_mirror<<<dim3(nlow / 64, (r1 - r0 + 63) / 64), 256, 0, st>>>((uint2*)PREDK, Vp, r0, r1, V, work, cap,
+                                                                               mirror_cnt, multi_cnt);
+            k_mirror_slow<K><<<1024, 256, 0, st>>>(work, mirror_cnt, cap, DST, npad, ent_ub, ent_w, cscoff, cscent,
+                                                   (uint2*)PREDK, Vp, multi_cnt);
+            HIP_CHECK(hipGetLastError());
+        };
+        std::vector<uint32_t> tri_h;  // the triangular launches' block lists (tri_scan_blocks), one after another
+        if (nloc) HIP_CHECK(hipStreamWaitEvent(st, c.ev_dst, 0));  // (the scan's DST, built on the aux stream)
+        // (a second pass only after a mirrored pass whose worklist overflowed)
+        for (bool again = nloc != 0; again;) {
+            again = false;
+            if (interleave) HIP_CHECK(hipMemsetAsync(&P.flags->changed, 0, 4, st));  // (loss_rounds: this pass's)
             const uint32_t inf_check = v5lo ? 0u : 1u;
             const uint32_t nbS5 = (uint32_t)(npad / SB);
             // host entry: the scan runs in source-block groups, each group's loss rows folded right
             // after it and shipped while later groups scan (loss rows on a second stream beside the
             // next group's scan were starved of CUs: 24.7 ms vs 20.8)
             const uint32_t ng = interleave ? std::min<uint32_t>(scan_groups, nbS5) : 1u;
+            // group bounds on multiples of 8 source blocks, in ascending order: a row's mirrored
+            // pairs read the packed rows before it (scan_group_cut / scan_group_cut_tri, plan.h)
+            auto cut = [&](uint32_t q) { return mirror ? scan_group_cut_tri(q, ng, nbS5) : scan_group_cut(q, ng, nbS5); };
+            const uint32_t* tri_d = nullptr;
+            std::vector<size_t> tri_off(ng + 1, 0);
+            if (mirror) {
+                tri_h.clear();
+                for (uint32_t gi = 0; gi < ng; ++gi) {
+                    tri_scan_blocks(cut(gi), cut(gi + 1), nbTT5, tri_h);
+                    tri_off[gi + 1] = tri_h.size();
+                }
+                uint32_t* d = (uint32_t*)c.b_tri.get(std::max<size_t>(tri_h.size(), 1) * 4);
+                if (!tri_h.empty()) HIP_CHECK(hipMemcpyAsync(d, tri_h.data(), tri_h.size() * 4, hipMemcpyHostToDevice, st));
+                HIP_CHECK(hipMemsetAsync(mirror_cnt, 0, 8, st));
+                tri_d = d;
+            }
             for (uint32_t gi = 0; gi < ng; ++gi) {
-                // group bounds on multiples of 8 source blocks (scan_group_cut, plan.h)
-                const uint32_t c0 = scan_group_cut(gi, ng, nbS5), c1 = scan_group_cut(gi + 1, ng, nbS5);
+                const uint32_t c0 = cut(gi), c1 = cut(gi + 1);
                 if (c1 == c0) continue;
-                const uint32_t nblk = (nbTT5 + 3) / 4 * ((c1 - c0 + 7) / 8);
-                tight_v5<<<8u * 32u * ((nblk + 7) / 8), V5_WAVES * 64, 0, st>>>(
-                    DSTs, npad, dsts_bytes, lnodes, nloc, V, NT, nbTT5, c1, nK5, c0, v5_goff,
-                    (const uint32_t*)c.b_entkey.get(0), PRED, Vp, inf_check);
+                // blocks of 4 target tiles x 8 source blocks; mirrored: those that touch the triangle
+                const uint32_t nblk = mirror ? (uint32_t)(tri_off[gi + 1] - tri_off[gi])
+                                             : (nbTT5 + 3) / 4 * ((c1 - c0 + 7) / 8);
+                if (nblk)
+                    tight_v5<<<8u * 32u * ((nblk + 7) / 8), V5_WAVES * 64, 0, st>>>(
+                        DSTs, npad, dsts_bytes, lnodes, nloc, V, NT, nbTT5, c1, nK5, c0, v5_goff,
+                        (const uint32_t*)c.b_entkey.get(0), PRED, Vp, inf_check, mirror ? tri_d + tri_off[gi] : nullptr);
                 HIP_CHECK(hipGetLastError());
                 if (interleave) {
                     const uint32_t r0 = c0 * SB, r1 = std::min<uint32_t>(c1 * SB, nloc);
                     if (r1 <= r0) continue;
                     pack_pred(r0, r1);
+                    if (mirror) mirror_rows(r0, r1);
                     k_loss_rows<K, true><<<r1 - r0, 1024, lds_rows, st>>>(PREDK, Vp, V, lnodes, nloc, ent_ub, ent_w,
                                                                    DST, npad, cscoff, cscent, P.selfloss, nodes, n,
-                                                                   lpos, out_loss, &P.flags->changed, r0);
+                                                                   lpos, out_loss, &P.flags->changed, r0,
+                                                                   mirror ? mirror_cnt + 1 : nullptr);
                     HIP_CHECK(hipGetLastError());
                     sink->send_rows(st, out_loss, sink->loss, pl.p0 + r0, r1 - r0, 4);
                 }
             }
             if (!PREDK) k_count_multi<<<nloc, kThreads, 0, st>>>(PRED, nloc, V, Vp, multi_cnt);  // (else k_pred_pack counted)
             HIP_CHECK(hipGetLastError());
-            ms_scan = tm.lap();
+            ms_scan += tm.lap();
             if (interleave) {  // loss rows already folded and shipped, group by group
                 sink->loss_sent = true;
                 rb_async(c, MS_CHANGED, &P.flags->changed, st);
+                if (mirror) rb_async(c, MS_MIRROR, mirror_cnt + 1, st);
                 HIP_CHECK(hipStreamSynchronize(st));
                 rounds = (int)rb_get<uint32_t>(c, MS_CHANGED);
                 loss_written = true;
@@ -431,6 +484,7 @@ bool run_dense(srg_ctx& c, const DevGraph& g, const Plan& pl, const uint32_t* no
                 HIP_CHECK(hipMemsetAsync(&P.flags->changed, 0, 4, st));
                 // host entry: row chunks, each chunk's loss rows sent as soon as it is done
                 pack_pred(0, nloc);
+                if (mirror) mirror_rows(0, nloc);
                 const uint32_t nchunk = std::max<uint32_t>(1, std::min<uint32_t>(c.loss_chunks ? c.loss_chunks : sink_rows ? 8 : 1, nloc));
                 for (uint32_t q = 0; q < nchunk; ++q) {
                     const uint32_t r0 = (uint32_t)((uint64_t)nloc * q / nchunk);
@@ -438,12 +492,14 @@ bool run_dense(srg_ctx& c, const DevGraph& g, const Plan& pl, const uint32_t* no
                     if (r1 == r0) continue;
                     k_loss_rows<K, true><<<r1 - r0, 1024, lds_rows, st>>>(PREDK, Vp, V, lnodes, nloc, ent_ub, ent_w,
                                                                    DST, npad, cscoff, cscent, P.selfloss, nodes, n,
-                                                                   lpos, out_loss, &P.flags->changed, r0);
+                                                                   lpos, out_loss, &P.flags->changed, r0,
+                                                                   mirror ? mirror_cnt + 1 : nullptr);
                     HIP_CHECK(hipGetLastError());
                     if (sink_rows) sink->send_rows(st, out_loss, sink->loss, pl.p0 + r0, r1 - r0, 4);
                 }
                 if (sink_rows) sink->loss_sent = true;
                 rb_async(c, MS_CHANGED, &P.flags->changed, st);
+                if (mirror) rb_async(c, MS_MIRROR, mirror_cnt + 1, st);
                 HIP_CHECK(hipStreamSynchronize(st));
                 rounds = (int)rb_get<uint32_t>(c, MS_CHANGED);
                 loss_written = true;
@@ -468,6 +524,21 @@ bool run_dense(srg_ctx& c, const DevGraph& g, const Plan& pl, const uint32_t* no
                     if (rounds > (int)V + 2) fail(SRG_ERR_INTERNAL, "loss rounds did not converge");
                 }
                 Lfin = Lin;
+            }
+            if (mirror) {
+                // (both mirrored branches above read the overflow word back with their last sync)
+                c.scan_mirrored = 1;
+                if (rb_get<uint32_t>(c, MS_MIRROR)) {
+                    // the worklist overflowed (a tie-heavy graph): some mirrored pairs are undecided.
+                    // The scan stage again with every pair scanned -- as the u64 rerun, one wasted
+                    // pass; every loss row is folded and shipped again
+                    c.scan_mirrored = 2;
+                    mirror = false;
+                    again = true;
+                    rounds = 0;
+                    loss_written = false;
+                    HIP_CHECK(hipMemsetAsync(multi_cnt, 0, 8, st));
+                }
             }
         }
     } else {

@@ -28,6 +28,8 @@ int srg_internal_compute_table(srg_ctx* ctx, const srg_edge_list* graph, const u
 // a table of at least `bytes` (*host: its address, 2 MB aligned): a recycled one from the pool, or
 // a fresh mapping (null: out of memory)
 srg_table* srg_internal_table_get(srg_ctx* ctx, size_t bytes, void** host);
+// plan.h's scan_group_cut_tri as run_dense calls it (the tests read the mirrored build's groups)
+uint32_t srg_internal_scan_group_cut_tri(uint32_t q, uint32_t ng, uint32_t nblocks);
 // back to its pool (still page-locked), or freed when the pool is closed or full
 void srg_internal_table_put(srg_table* t);
 }

@@ -107,4 +107,47 @@ inline uint32_t scan_group_cut(uint32_t q, uint32_t ng, uint32_t nblocks) {
     return std::min(nblocks, (nblocks * q / ng + 4) / 8 * 8);
 }
 
+// ---- triangular scan (undirected one-rank builds: SRG_OPT_SCAN_MIRROR) ----
+// tight_v5 then scans only the (source block c, target tile b) pairs with b >= c; the pairs below
+// the diagonal are derived from them (k_pred_mirror).  Its launch unit stays the block of 4 target
+// tiles x 8 source blocks that one XCD holds at once (the workgroups of a block share record
+// streams and staged rows), so a launch over the source blocks [c0, c1) lists the blocks that touch
+// the triangle: descriptor = (index of the 4-tile group) | (index of the 8-source-block group,
+// counted from c0) << 16, source groups outermost as in the full launch.  Workgroups of a listed
+// block that lie under the diagonal return at once.  The list is padded to a multiple of 8 with
+// TRI_PAD: the blocks are dealt to the 8 XCDs in turn.
+constexpr uint32_t TRI_PAD = 0xFFFFFFFFu;
+inline void tri_scan_blocks(uint32_t c0, uint32_t c1, uint32_t ntiles, std::vector<uint32_t>& out) {
+    const size_t base = out.size();
+    if (ntiles && c1 > c0)
+        for (uint32_t sg = 0; c0 + 8 * sg < c1; ++sg)
+            for (uint32_t tb = 0; 4 * tb < ntiles; ++tb)
+                if (std::min(4 * tb + 3, ntiles - 1) >= c0 + 8 * sg) out.push_back(tb | sg << 16);
+    while ((out.size() - base) % 8) out.push_back(TRI_PAD);
+}
+
+// scan-group cut for the triangular scan: source block c scans nblocks - c target tiles, so the
+// work of the blocks [0, c) is tri_scan_work(c).  As scan_group_cut, bounds lie on multiples of 8
+// blocks (each XCD the same number of source blocks per launch) and the last group is the last
+// partial 8 blocks (few loss rows left to ship after the last fold).  Of the blocks before it the
+// first group takes half the triangular work (the latency rows hold the link while it scans: C3 24
+// of 72 blocks); further groups split the rest evenly by rows -- their scan is cheap, their loss
+// rows are what the link waits for.  Each cut rounded to the nearest multiple of 8.
+inline uint64_t tri_scan_work(uint32_t c, uint32_t nblocks) { return (uint64_t)c * nblocks - (uint64_t)c * (c ? c - 1 : 0) / 2; }
+inline uint32_t scan_group_cut_tri(uint32_t q, uint32_t ng, uint32_t nblocks) {
+    if (q == 0) return 0u;
+    if (q >= ng) return nblocks;
+    const uint32_t last = nblocks ? (nblocks - 1) / 8 * 8 : 0u;
+    const bool tail = ng >= 3 && last > 0;       // the last group = the blocks [last, nblocks)
+    const uint32_t end = tail ? last : nblocks;  // the blocks the other groups split
+    const uint32_t parts = tail ? ng - 1 : ng;
+    if (q >= parts) return end;
+    const uint64_t want = tri_scan_work(end, nblocks) / 2;
+    uint32_t c = 0;
+    while (c < end && tri_scan_work(c, nblocks) < want) ++c;
+    const uint32_t half = std::min(end, (c + 4) / 8 * 8);
+    if (q == 1) return half;
+    return std::min(end, half + ((end - half) * (q - 1) / (parts - 1) + 4) / 8 * 8);
+}
+
 }  // namespace

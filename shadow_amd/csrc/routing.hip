@@ -798,7 +798,7 @@ struct srg_ctx {
     int edge_shard = -1;             // host entry, multi-rank: ship 1/N of the edges, allgatherv the rest (SRG_OPT_EDGE_SHARD)
     const uint32_t* sim_edges = nullptr;  // simulated rank: the edge list whose other slices are resident
     size_t sim_E = 0;
-    int scan_groups = 0;             // host entry: v5 scan launches interleaved with the loss rows (0 = auto: 3) (SRG_OPT_SCAN_GROUPS)
+    int scan_groups = 0;             // host entry: v5 scan launches interleaved with the loss rows (0 = auto: 3, mirrored scan 4) (SRG_OPT_SCAN_GROUPS)
     int loss_chunks = 0;             // k_loss_rows launches (0 = auto: 8 when the host entry ships rows early, else 1) (SRG_OPT_LOSS_CHUNKS)
     srg::Comm* comm = nullptr;       // null = single GPU
     // srg_multi: the caller's output arrays are page-locked once for every rank (portable); the
@@ -839,6 +839,10 @@ struct srg_ctx {
     DevBuf b_odiag;
     int fw_overlap = 1;                 // host entry: FW starts while the edge list arrives (SRG_OPT_FW_OVERLAP)
     int fw_xcd_order = 1;               // symmetric FW bulk: tiles dealt to the XCDs in Z-order runs (SRG_OPT_FW_XCD_ORDER)
+    int scan_mirror = 1;                // undirected one-rank builds: scan the pairs (tile >= source block), mirror the rest (SRG_OPT_SCAN_MIRROR)
+    int scan_mirrored = 0;              // the last build: 0 = every pair scanned, 1 = mirrored, 2 = mirrored, then rescanned (SRG_OPT_SCAN_MIRRORED)
+    int scan_mirror_cap = 0;            // the mirror worklist's capacity in pairs per launch (0 = 1 / 1024 of the rows' pairs) (SRG_OPT_SCAN_MIRROR_CAP)
+    DevBuf b_tri;                       // the triangular scan launches' block lists
     int test_fault = 0;                 // TEST HOOK (SRG_OPT_TEST_FAULT): 1 = zero D after FW, 2 = stale FW sync words
     std::shared_ptr<TablePool> tpool = std::make_shared<TablePool>();  // RoutingInfo's pinned tables
     double ms_create_runtime = 0, ms_create_lib = 0;  // srg_create: HIP runtime / device init vs the library's own
@@ -967,7 +971,7 @@ T rb_get(const srg_ctx& c, int slot) {
     std::memcpy(&v, c.hbox + 64 * slot, sizeof(T));
     return v;
 }
-enum MailSlot { MS_EDGESTATS, MS_FLAGS, MS_TIMEOUT, MS_REDUCE, MS_TAIL0, MS_TAIL1, MS_NMULTI, MS_CHANGED, MS_MIN, MS_REDUCE2 };
+enum MailSlot { MS_EDGESTATS, MS_FLAGS, MS_TIMEOUT, MS_REDUCE, MS_TAIL0, MS_TAIL1, MS_NMULTI, MS_CHANGED, MS_MIN, MS_REDUCE2, MS_MIRROR };
 
 // Common validation: nodes in range & unique, edge endpoints, self-loop counts, latency range.
 struct Prelude {
@@ -2154,6 +2158,7 @@ void compute_device(srg_ctx& c, const DevGraph& g, const uint32_t* nodes, uint32
                     FwOverlap* ov = nullptr) {
     HIP_CHECK(hipStreamSynchronize(c.aux_stream));  // nothing of an aborted call still writes WL / PRED
     HIP_CHECK(hipStreamSynchronize(c.comm_stream));  // ... or the essential-entry counts
+    c.scan_mirrored = 0;
     if (g.V == 0) {
         if (n) fail(SRG_ERR_ARG, "nodes given for an empty graph");
         return;
@@ -3330,6 +3335,14 @@ int srg_set_option(srg_ctx* ctx, int option, double value) {
             if (value != 0 && value != 1) return SRG_ERR_ARG;
             ctx->fw_xcd_order = (int)value;
             return SRG_OK;
+        case SRG_OPT_SCAN_MIRROR:
+            if (value != 0 && value != 1) return SRG_ERR_ARG;
+            ctx->scan_mirror = (int)value;
+            return SRG_OK;
+        case SRG_OPT_SCAN_MIRROR_CAP:
+            if (!(value >= 0 && value <= 1073741824.0)) return SRG_ERR_ARG;
+            ctx->scan_mirror_cap = (int)value;
+            return SRG_OK;
         case SRG_OPT_TABLE_POOL_BYTES: {
             if (!(value >= 0.0 && value <= 1e15)) return SRG_ERR_ARG;
             std::lock_guard<std::mutex> pl(ctx->tpool->mu);
@@ -3383,6 +3396,9 @@ int srg_get_option(srg_ctx* ctx, int option, double* value) {
         case SRG_OPT_CREATE_MS_RUNTIME: *value = ctx->ms_create_runtime; break;
         case SRG_OPT_FW_XCD_ORDER: *value = ctx->fw_xcd_order; break;
         case SRG_OPT_CREATE_MS_LIBRARY: *value = ctx->ms_create_lib; break;
+        case SRG_OPT_SCAN_MIRROR: *value = ctx->scan_mirror; break;
+        case SRG_OPT_SCAN_MIRRORED: *value = ctx->scan_mirrored; break;
+        case SRG_OPT_SCAN_MIRROR_CAP: *value = ctx->scan_mirror_cap; break;
         default: return SRG_ERR_ARG;
     }
     return SRG_OK;
@@ -3409,6 +3425,10 @@ int srg_internal_compute_table(srg_ctx* ctx, const srg_edge_list* graph, const u
                               !shortest, out_key, out_diag, tabs);
     if (unit_ns) *unit_ns = out_key && st->latency_unit_ns ? st->latency_unit_ns : 1;
     return rc;
+}
+
+uint32_t srg_internal_scan_group_cut_tri(uint32_t q, uint32_t ng, uint32_t nblocks) {
+    return scan_group_cut_tri(q, ng, nblocks);
 }
 
 srg_table* srg_internal_table_get(srg_ctx* ctx, size_t bytes, void** host) {

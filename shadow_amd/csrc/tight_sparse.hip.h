@@ -246,16 +246,30 @@ struct alignas(64) V5Grp {
 // rows by 4, and both come out of that XCD's L2 after the first read.  (With one source block per
 // XCD the rows were shared 64 ways, but every record stream came from the Infinity Cache, and the
 // scalar record loads are what each group waits for.)
+// With `tri` (undirected one-rank builds) the launch lists only the blocks that hold
+// a pair with target tile >= source block (tri_scan_blocks, plan.h; the grid covers the padded
+// list), a workgroup under the diagonal returns at once, and k_pred_mirror derives those pairs.
 __global__ void __launch_bounds__(512, 4) tight_v5(const uint32_t* __restrict__ DST, size_t npad, uint32_t dst_bytes,
                                                     const uint32_t* __restrict__ nodes, uint32_t n, uint32_t V,
                                                     uint32_t NT, uint32_t nbTT, uint32_t nbS, uint32_t nK, uint32_t c0,
                                                     const uint32_t* __restrict__ goff, const uint32_t* __restrict__ rec,
-                                                    uint32_t* __restrict__ PRED, size_t ldp, uint32_t inf_check) {
+                                                    uint32_t* __restrict__ PRED, size_t ldp, uint32_t inf_check,
+                                                    const uint32_t* __restrict__ tri) {
     __shared__ __attribute__((aligned(16))) uint32_t rows[2 * V5_UC * V5_SB];  // 2 x 32 KB ring
     const uint32_t bid = blockIdx.x, xcd = bid & 7, slot = bid >> 3;
     const uint32_t blk = (slot >> 5) * 8 + xcd, nbb = (nbTT + 3) / 4;  // block of 4 tiles x 8 source blocks
-    const uint32_t b = (blk % nbb) * 4 + (slot & 3), c = c0 + (blk / nbb) * 8 + ((slot >> 2) & 7);
+    uint32_t tb = blk % nbb, sg = blk / nbb;
+    if (tri) {
+        // triangular launch (tri_scan_blocks, plan.h): block `blk` of the list of blocks that touch
+        // the pairs (tile b >= source block c); the grid covers the padded list exactly
+        const uint32_t d = tri[blk];
+        if (d == 0xFFFFFFFFu) return;
+        tb = d & 0xFFFFu;
+        sg = d >> 16;
+    }
+    const uint32_t b = tb * 4 + (slot & 3), c = c0 + sg * 8 + ((slot >> 2) & 7);
     if (c >= nbS || b >= nbTT) return;  // whole workgroup: no barrier is left waiting
+    if (tri && b < c) return;           // under the diagonal: derived by k_pred_mirror
     const uint32_t tid = threadIdx.x, lane = tid & 63;
     const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane(tid >> 6);
     const uint32_t r0 = c * V5_SB + 2 * lane;  // this lane's two sources (columns of DST)
@@ -384,10 +398,12 @@ __global__ void __launch_bounds__(512, 4) tight_v5(const uint32_t* __restrict__ 
 __global__ void __launch_bounds__(256) k_pred_pack(const uint32_t* __restrict__ PRED, size_t ldp, uint32_t r0,
                                                    uint32_t r1, uint32_t NT, uint32_t nbTT, uint32_t nsb,
                                                    const uint2* __restrict__ ent_ub, uint2* __restrict__ PK,
-                                                   unsigned long long* __restrict__ multi) {
+                                                   unsigned long long* __restrict__ multi, uint32_t tri) {
     const uint32_t xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
     const uint32_t b = xcd + 8 * (slot / nsb), sb = slot % nsb;
     if (b >= nbTT) return;
+    // triangular scan (r0 on a source-block bound): tight_v5 wrote only the tiles b >= source block
+    if (tri && b < r0 / V5_SB + sb) return;
     const uint32_t tx = threadIdx.x & 31, ty = threadIdx.x >> 5;  // 32 x 8: 4 targets per thread
     const uint32_t t = b * V5_TT + tx * 4;
     const bool tv = t < NT;  // (tight_v5 writes targets < NT = V rounded up to 64; a multiple of 4)
@@ -426,6 +442,125 @@ __global__ void __launch_bounds__(256) k_pred_pack(const uint32_t* __restrict__ 
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) nm += __shfl_xor(nm, o, 64);
         if ((threadIdx.x & 63) == 0) atomicAdd(multi, (unsigned long long)nm);
+    }
+}
+
+// ---- mirrored pairs of the triangular scan (undirected graph, rows = vertices in order) --------
+// PK[t][s] for the rows t of [r0, r1) and the columns s with blk(s) < blk(t) (blk = index / 128),
+// which tight_v5 skipped, from the scanned part of PK (blk(column) >= blk(row)).  D and W are
+// symmetric, so the tight predecessors of s from t are the first hops from s toward t.  Walk back
+// from x = t along row s:
+//   blk(x) < blk(s):   every shortest s-t path ends with the walked x ... t, so the first hops
+//                      toward t are those toward x: the scanned PK[x][s], copied whole (a
+//                      PRED_MULTI there is exact);
+//   v = PK[s][x].u (scanned, blk(x) >= blk(s)):  v == s: x is the only first hop, and the edge
+//                      (x, s) is the undirected edge (s, x): {x, PK[s][x].b};
+//                      v no vertex (PRED_MULTI / PRED_NONE): the exact path below;
+//                      else x = v.
+// Every set met before the last step is a singleton, so the s-t shortest path is unique up to x and
+// the result is exact.  At most MIRROR_STEPS steps, then the exact path as well: the pair goes to
+// the worklist work[0 .. cap) (wcnt[0] = pairs wanted, wcnt[1] = 1 once one did not fit) and
+// k_mirror_slow decides it from the exact keys, as k_loss_round_sparse decides a MULTI target.
+// Once wcnt[1] is set both kernels return at once, in this launch and in every later group's.
+// Workgroup = 64 rows t (lanes) x 64 columns s (16 per wave): a wave's first read PK[s][t] is
+// coalesced and its walk stays in row s; the results leave by rows through an LDS transpose.
+// grid: (ceil(lower columns / 64), 64-row tiles of [r0, r1)), r0 a multiple of 128.
+constexpr uint32_t MIRROR_STEPS = 64;
+__global__ void __launch_bounds__(256) k_pred_mirror(uint2* __restrict__ PK, size_t ldp, uint32_t r0, uint32_t r1,
+                                                     uint32_t V, uint2* __restrict__ work, uint32_t cap,
+                                                     uint32_t* __restrict__ wcnt,
+                                                     unsigned long long* __restrict__ multi) {
+    __shared__ uint2 tile[64][65];
+    __shared__ uint32_t overflowed;
+    const uint32_t tt = r0 / 64 + blockIdx.y, sc = blockIdx.x * 64;
+    if (sc >= tt / 2 * V5_SB) return;  // whole workgroup: at or past the rows' diagonal block
+    // an overflowed worklist (this launch's or an earlier group's): the host scans every pair again,
+    // nothing written from here on is read.  One read per workgroup, so all its waves agree.
+    if (threadIdx.x == 0) overflowed = wcnt[1];
+    __syncthreads();
+    if (overflowed) return;
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t t = tt * 64 + lane;
+    uint32_t nm = 0;
+    for (uint32_t i = 0; i < 16; ++i) {
+        const uint32_t sl = wave * 16 + i, s = sc + sl, bs = s / V5_SB;
+        uint2 res = make_uint2(PRED_NONE, 0u);
+        if (t < r1) {
+            const uint2* rs = PK + (size_t)s * ldp;
+            uint32_t x = t;
+            bool slow = true;
+            for (uint32_t step = 0; step < MIRROR_STEPS; ++step) {
+                if (x / V5_SB < bs) {
+                    res = PK[(size_t)x * ldp + s];
+                    slow = false;
+                    break;
+                }
+                const uint2 e = rs[x];
+                if (e.x == s) {
+                    res = make_uint2(x, e.y);
+                    slow = false;
+                    break;
+                }
+                if (e.x >= V) break;
+                x = e.x;
+            }
+            if (slow) {
+                const uint32_t q = atomicAdd(&wcnt[0], 1u);
+                if (q < cap) work[q] = make_uint2(t, s);
+                else wcnt[1] = 1u;
+            } else {
+                nm += res.x == PRED_MULTI;
+            }
+        }
+        tile[lane][sl] = res;
+    }
+    __syncthreads();
+    // 32 threads x 16 B per row of 64 results, 8 rows per pass
+    const uint32_t c2 = (threadIdx.x & 31) * 2;
+    for (uint32_t row = threadIdx.x >> 5; row < 64; row += 8) {
+        const uint32_t tr = tt * 64 + row;
+        if (tr >= r1) break;
+        const uint2 a = tile[row][c2], b = tile[row][c2 + 1];
+        *reinterpret_cast<uint4*>(PK + (size_t)tr * ldp + sc + c2) = make_uint4(a.x, a.y, b.x, b.y);
+    }
+    if (__ballot(nm != 0)) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) nm += __shfl_xor(nm, o, 64);
+        if (lane == 0) atomicAdd(multi, (unsigned long long)nm);
+    }
+}
+
+// one wave per worklist pair (row t, column s): every CSC entry (u -> s) against the exact keys
+template <class K>
+__global__ void __launch_bounds__(256) k_mirror_slow(const uint2* __restrict__ work, const uint32_t* __restrict__ wcnt,
+                                                     uint32_t cap, const K* __restrict__ DST, size_t npad,
+                                                     const uint2* __restrict__ ent_ub, const K* __restrict__ ent_w,
+                                                     const uint32_t* __restrict__ csc_off,
+                                                     const uint32_t* __restrict__ csc_ent, uint2* __restrict__ PK,
+                                                     size_t ldp, unsigned long long* __restrict__ multi) {
+    const uint32_t lane = threadIdx.x & 63;
+    if (wcnt[1]) return;  // overflowed: the host scans every pair again (no barrier in this kernel)
+    const uint32_t nw = min(wcnt[0], cap), nwaves = gridDim.x * (blockDim.x >> 6);
+    for (uint32_t i = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); i < nw; i += nwaves) {
+        const uint2 ts = work[i];
+        const uint32_t t = ts.x, s = ts.y;
+        const K dst = DST[(size_t)s * npad + t];
+        uint32_t cnt = 0, hit = 0;
+        for (uint32_t k = csc_off[s] + lane; k < csc_off[s + 1]; k += 64) {
+            const uint32_t e = csc_ent[k];
+            if (KeyOps<K>::add(DST[(size_t)ent_ub[e].x * npad + t], ent_w[e]) != dst) continue;
+            ++cnt;
+            hit = e;
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            cnt += __shfl_xor(cnt, o, 64);
+            hit = max(hit, (uint32_t)__shfl_xor(hit, o, 64));
+        }
+        if (lane == 0) {
+            PK[(size_t)t * ldp + s] = cnt == 1 ? ent_ub[hit] : make_uint2(cnt ? PRED_MULTI : PRED_NONE, 0u);
+            if (cnt > 1) atomicAdd(multi, 1ull);
+        }
     }
 }
 
@@ -496,7 +631,11 @@ __global__ void __launch_bounds__(1024) k_loss_rows(const uint32_t* __restrict__
                                                      const float* __restrict__ self_loss,
                                                      const uint32_t* __restrict__ cols, uint32_t ncols,
                                                      const uint32_t* __restrict__ rowpos, float* __restrict__ out_loss,
-                                                     uint32_t* __restrict__ max_sweeps, uint32_t row0) {
+                                                     uint32_t* __restrict__ max_sweeps, uint32_t row0,
+                                                     const uint32_t* __restrict__ skip) {
+    // mirrored scan whose worklist overflowed (set by an earlier launch on this stream, so the whole
+    // grid agrees): the table is incomplete and the host runs the stage again -- nothing to fold
+    if (skip && *skip) return;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     uint32_t* U = reinterpret_cast<uint32_t*>(smem_raw);
     float* Bf = reinterpret_cast<float*>(U + V);
