@@ -382,8 +382,9 @@ int srg_multi_get_direct_paths(srg_multi* m, const srg_edge_list* graph, const u
  * num_nodes x num_nodes output of srg_compute_shortest_paths (rows = sending node position).
  * Outputs: deliver_ns[i] per event; order = event indices grouped by destination host
  * (increasing HostId), each host's events in its queue's pop order; host_offsets[h] ..
- * host_offsets[h+1] = host h's slice.  The packet-drop draw (worker.rs:374-389) consumes each
- * host's RNG stream in program order and is not part of the batch.                          */
+ * host_offsets[h+1] = host h's slice.  This entry starts at the latency lookup: the packet-drop
+ * decision (worker.rs:374-390) and increment_packet_count (:395) above it are covered by
+ * srg_send_packets_device below, which takes the host-drawn `chance` values as an array.     */
 #define SRG_ERR_EVENT_ORDER 11  /* two events with no relative order: PanickingOrd unwrap panic
                                    (event.rs:141-147, event_queue.rs:87-90) */
 typedef struct srg_event_batch {
@@ -413,6 +414,64 @@ int srg_order_packet_events_device(srg_ctx* ctx, const srg_event_batch* batch_de
                                    uint64_t* out_deliver_ns_dev, uint32_t* out_order_dev,
                                    uint64_t* out_host_offsets_dev, void* hip_stream,
                                    srg_event_result* result, char* errbuf, size_t errlen);
+
+/* ---- the whole per-packet tail of Worker::send_packet, batched --------------------------
+ * srg_order_packet_events_device plus the lines above its start (worker.rs:374-395):
+ *   reliability = 1.0f32 - packet_loss(src, dst), widened to f64      (worker.rs:563-568)
+ *   dropped iff !is_bootstrapping && chance >= reliability && payload_size > 0   (:374-390)
+ *   increment_packet_count(src, dst) for every packet sent             (:395, mod.rs:449-456)
+ * against the table in either form a RoutingInfo keeps (u64 ns, or the build's u32 keys: no
+ * widening, srg_routing_info_key_tables).  Only the RNG stays on the host: `chance` is
+ * src_host.random_mut().gen::<f64>(), drawn unconditionally for every packet (worker.rs:377), so
+ * the caller draws it per packet in program order and hands the array over.
+ * Left to the caller, before an event enters the batch: the is_completed early return
+ * (worker.rs:336-343) and the drop of a packet whose dst_ip resolves to no host (no dst_host to
+ * give: dst_host >= num_hosts stays SRG_ERR_ARG).  Neither consumes a draw the batch could see.
+ * Outputs: status[i] = 1 sent (PDS_INET_SENT) / 0 dropped (PDS_INET_DROPPED); deliver_ns[i], or
+ * UINT64_MAX for a dropped event; order = the num_sent sent indices, grouped and ordered as above
+ * (out_order_dev holds num_events slots, num_sent are written); host_offsets[num_hosts] = num_sent.
+ * A dropped event takes no part in anything after its decision: the overflow check of send +
+ * latency, the minima, the equal-key check (SRG_ERR_EVENT_ORDER), order and offsets.  The node and
+ * dst_host range checks apply to every event.
+ * packet_counts_dev (may be NULL): caller-owned [n*n] u64 by node position, NOT cleared --
+ * accumulated across calls; [src_node, dst_node] += 1 per sent event, saturating at UINT64_MAX.
+ * The counters move as soon as the range checks passed (also when the call then returns
+ * SRG_ERR_EVENT_ORDER).  Merge them into a RoutingInfo with srg_routing_info_add_packet_counts. */
+typedef struct srg_path_table_dev {   /* routing table resident in HBM, indexed by node position */
+    uint32_t n, reserved;
+    const uint64_t* latency_ns;   /* [n*n] u64 ns, or NULL when latency_key is given            */
+    const uint32_t* latency_key;  /* [n*n] u32 keys: latency = key * unit_ns off the diagonal   */
+    const uint64_t* diag_ns;      /* [n]   with latency_key: raw self-loop latency per position */
+    uint64_t unit_ns;             /*       with latency_key                                     */
+    const float* packet_loss;     /* [n*n]; NULL = no drop decision, every packet is sent       */
+} srg_path_table_dev;
+
+typedef struct srg_send_batch {
+    srg_event_batch ev;           /* as srg_order_packet_events_device                          */
+    const double* chance;         /* [n] host-drawn f64 in [0,1), program order (worker.rs:377) */
+    const uint32_t* payload_size; /* [n] packet_getPayloadSize, only > 0 matters                */
+    uint64_t bootstrap_end_ns;    /* sends before it are never dropped (worker.rs:337-338)      */
+} srg_send_batch;
+
+typedef struct srg_send_result { srg_event_result ev; uint64_t num_sent, num_dropped; } srg_send_result;
+
+/* SRG_ERR_ARG unless exactly one of latency_ns / latency_key is given, diag_ns and unit_ns >= 1
+ * come with latency_key, and chance and payload_size come with packet_loss.                    */
+int srg_send_packets_device(srg_ctx* ctx, const srg_send_batch* batch_dev, const srg_path_table_dev* table,
+                            uint8_t* out_status_dev, uint64_t* out_deliver_ns_dev, uint32_t* out_order_dev,
+                            uint64_t* out_host_offsets_dev, uint64_t* packet_counts_dev /* may be NULL */,
+                            void* hip_stream, srg_send_result* result, char* errbuf, size_t errlen);
+
+/* A RoutingInfo whose table kept the build's u32 keys (srg_stats.table_keys = 1): returns 1 and
+ * borrowed host views (key [n*n], diag_ns [n], unit_ns, packet_loss [n*n]) -- what
+ * srg_path_table_dev takes, uploaded as they are.  Returns 0 for a u64 table (use
+ * srg_routing_info_tables).  Never builds the u64 view that srg_routing_info_tables widens.     */
+int srg_routing_info_key_tables(const srg_routing_info* ri, const uint32_t** key, const uint64_t** diag_ns,
+                                uint64_t* unit_ns, const float** packet_loss, uint32_t* n);
+/* Merges a batch counter table (packet_counts_dev copied to the host, n*n by position) into the
+ * counters behind increment_packet_count / packet_count: every nonzero entry is saturating-added
+ * under the GML ids of its positions.  Thread-safe against the per-packet calls.                */
+void srg_routing_info_add_packet_counts(srg_routing_info* ri, const uint64_t* counts_by_position /* host, n*n */);
 
 /* Library build/version string. */
 const char* srg_version(void);

@@ -112,6 +112,40 @@ class EventResult(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class PathTableDev(ctypes.Structure):
+    _fields_ = [
+        ("n", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32),
+        ("latency_ns", ctypes.c_void_p),
+        ("latency_key", ctypes.c_void_p),
+        ("diag_ns", ctypes.c_void_p),
+        ("unit_ns", ctypes.c_uint64),
+        ("packet_loss", ctypes.c_void_p),
+    ]
+
+
+class SendBatch(ctypes.Structure):
+    _fields_ = [
+        ("ev", EventBatch),
+        ("chance", ctypes.c_void_p),
+        ("payload_size", ctypes.c_void_p),
+        ("bootstrap_end_ns", ctypes.c_uint64),
+    ]
+
+
+class SendResult(ctypes.Structure):
+    _fields_ = [
+        ("ev", EventResult),
+        ("num_sent", ctypes.c_uint64),
+        ("num_dropped", ctypes.c_uint64),
+    ]
+
+    def as_dict(self):
+        d = self.ev.as_dict()
+        d.update(num_sent=self.num_sent, num_dropped=self.num_dropped)
+        return d
+
+
 class Stats(ctypes.Structure):
     _fields_ = [
         ("ms_total", ctypes.c_double),
@@ -164,6 +198,7 @@ EXPORTS = [
     "srg_routing_info_smallest_latency_ns", "srg_routing_info_tables",
     "srg_multi_create", "srg_multi_destroy", "srg_multi_size", "srg_multi_set_option", "srg_multi_compute_shortest_paths",
     "srg_multi_get_direct_paths", "srg_routing_info_build_multi", "srg_get_option",
+    "srg_send_packets_device", "srg_routing_info_key_tables", "srg_routing_info_add_packet_counts",
 ]
 
 _lib = None
@@ -243,6 +278,15 @@ def lib():
     L.srg_order_packet_events_device.argtypes = [
         c.c_void_p, c.POINTER(EventBatch), c.c_void_p, c.c_uint32, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p,
         c.POINTER(EventResult), c.c_char_p, c.c_size_t]
+    L.srg_send_packets_device.restype = c.c_int
+    L.srg_send_packets_device.argtypes = [
+        c.c_void_p, c.POINTER(SendBatch), c.POINTER(PathTableDev), c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p,
+        c.c_void_p, c.c_void_p, c.POINTER(SendResult), c.c_char_p, c.c_size_t]
+    L.srg_routing_info_key_tables.restype = c.c_int
+    L.srg_routing_info_key_tables.argtypes = [c.c_void_p, c.POINTER(_u32p), c.POINTER(_u64p), _u64p, c.POINTER(_f32p),
+                                              c.POINTER(c.c_uint32)]
+    L.srg_routing_info_add_packet_counts.restype = None
+    L.srg_routing_info_add_packet_counts.argtypes = [c.c_void_p, c.c_void_p]
     L.srg_routing_info_build.restype = c.c_int
     L.srg_routing_info_build.argtypes = [c.c_void_p, c.POINTER(EdgeList), c.c_void_p, c.c_uint32, c.c_int,
                                          c.POINTER(c.c_void_p), c.POINTER(Stats), c.c_char_p, c.c_size_t]

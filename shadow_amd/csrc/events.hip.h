@@ -12,8 +12,10 @@
 //   EventQueue pop order (event_queue.rs:38-49): Event::partial_cmp (event.rs:84-155) = time,
 //     then Packet < Local, then src_host_id, then src_host_event_id; two events equal in all of
 //     these (different packets) have no order -> PanickingOrd unwrap panic -> SRG_ERR_EVENT_ORDER.
-// The packet-drop draw (worker.rs:374-389) consumes each source host's RNG stream in program
-// order and stays on the host.
+// srg_order_packet_events_device starts at the latency lookup.  srg_send_packets_device starts at
+// the top of the tail: the drop decision (worker.rs:374-390) and increment_packet_count (:395) too.
+// Only the RNG draw stays on the host: it consumes each source host's stream in program order,
+// unconditionally per packet, so the host hands the drawn `chance` values over as an array.
 //
 // Device design: one pass computes deliver times and the batch's field ranges (min/max); the
 // host then packs every event into one composite key of only the bits the batch uses
@@ -24,6 +26,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "send_rule.h"
 
 namespace srg {
 
@@ -64,39 +68,12 @@ __device__ __forceinline__ T wave_max(T v) {
     return v;
 }
 
-__global__ void __launch_bounds__(256) k_ev_prep(EvIn in, uint64_t* __restrict__ deliver, EvReduce* red) {
-    unsigned long long tmin = ~0ull, tmax = 0, imin = ~0ull, imax = 0, lmin = ~0ull;
-    uint32_t dmax = 0, smax = 0, bad = 0;
-    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < in.n; i += (size_t)gridDim.x * blockDim.x) {
-        const uint32_t a = in.src_node[i], b = in.dst_node[i], dh = in.dst_host[i], sh = in.src_host[i];
-        if (a >= in.tn || b >= in.tn) {
-            bad |= 2;
-            continue;
-        }
-        if (dh >= in.num_hosts) {
-            bad |= 1;
-            continue;
-        }
-        const uint64_t delay = in.table[(size_t)a * in.tn + b];
-        const uint64_t s = in.send_ns[i];
-        if (s > ~0ull - delay) {
-            bad |= 4;
-            continue;
-        }
-        uint64_t t = s + delay;
-        t = t < in.round_end ? in.round_end : t;
-        deliver[i] = t;
-        const uint64_t id = in.event_id[i];
-        tmin = t < tmin ? t : tmin;
-        tmax = t > tmax ? t : tmax;
-        imin = id < imin ? id : imin;
-        imax = id > imax ? id : imax;
-        lmin = delay < lmin ? delay : lmin;
-        dmax = dh > dmax ? dh : dmax;
-        smax = sh > smax ? sh : smax;
-    }
-    // wave, then workgroup reduction: one set of same-address atomics per workgroup (a grid of
-    // ~2k workgroups), not per wave -- same-address atomics serialise at the memory side
+// wave, then workgroup reduction: one set of same-address atomics per workgroup (a grid of
+// ~2k workgroups), not per wave -- same-address atomics serialise at the memory side
+__device__ __forceinline__ void ev_block_reduce(unsigned long long tmin, unsigned long long tmax,
+                                                unsigned long long imin, unsigned long long imax,
+                                                unsigned long long lmin, uint32_t dmax, uint32_t smax, uint32_t bad,
+                                                EvReduce* red) {
     tmin = wave_min(tmin);
     tmax = wave_max(tmax);
     imin = wave_min(imin);
@@ -139,6 +116,149 @@ __global__ void __launch_bounds__(256) k_ev_prep(EvIn in, uint64_t* __restrict__
     }
 }
 
+__global__ void __launch_bounds__(256) k_ev_prep(EvIn in, uint64_t* __restrict__ deliver, EvReduce* red) {
+    unsigned long long tmin = ~0ull, tmax = 0, imin = ~0ull, imax = 0, lmin = ~0ull;
+    uint32_t dmax = 0, smax = 0, bad = 0;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < in.n; i += (size_t)gridDim.x * blockDim.x) {
+        const uint32_t a = in.src_node[i], b = in.dst_node[i], dh = in.dst_host[i], sh = in.src_host[i];
+        if (a >= in.tn || b >= in.tn) {
+            bad |= 2;
+            continue;
+        }
+        if (dh >= in.num_hosts) {
+            bad |= 1;
+            continue;
+        }
+        const uint64_t delay = in.table[(size_t)a * in.tn + b];
+        const uint64_t s = in.send_ns[i];
+        if (s > ~0ull - delay) {
+            bad |= 4;
+            continue;
+        }
+        uint64_t t = s + delay;
+        t = t < in.round_end ? in.round_end : t;
+        deliver[i] = t;
+        const uint64_t id = in.event_id[i];
+        tmin = t < tmin ? t : tmin;
+        tmax = t > tmax ? t : tmax;
+        imin = id < imin ? id : imin;
+        imax = id > imax ? id : imax;
+        lmin = delay < lmin ? delay : lmin;
+        dmax = dh > dmax ? dh : dmax;
+        smax = sh > smax ? sh : smax;
+    }
+    ev_block_reduce(tmin, tmax, imin, imax, lmin, dmax, smax, bad, red);
+}
+
+// ---- the whole of send_packet (srg_send_packets_device) -------------------------------------
+// The prep pass with the drop decision in front (send_rule.h) and either table form behind it.
+// A dropped event gets status 0 and deliver = UINT64_MAX and feeds no reduction: the reference
+// returns before the latency lookup (worker.rs:381-389), so it can neither overflow send + delay
+// nor widen a key field nor lower a minimum.  The key pass parks it behind host `num_hosts`
+// (k_ev_keys<.., true>) and the finish pass leaves the parked run out of the equal-key check.
+struct EvSendIn {
+    PathLatency tab;
+    const float* loss;  // [tn x tn], null: every packet is sent
+    const double* chance;
+    const uint32_t* payload;
+    uint64_t bootstrap_end;
+};
+
+struct EvSendReduce {
+    EvReduce r;
+    unsigned long long sent;
+};
+
+__global__ void __launch_bounds__(256) k_ev_send_prep(EvIn in, EvSendIn sx, uint8_t* __restrict__ status,
+                                                      uint64_t* __restrict__ deliver, EvSendReduce* red) {
+    unsigned long long tmin = ~0ull, tmax = 0, imin = ~0ull, imax = 0, lmin = ~0ull;
+    uint32_t dmax = 0, smax = 0, bad = 0, sent = 0;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < in.n; i += (size_t)gridDim.x * blockDim.x) {
+        const uint32_t a = in.src_node[i], b = in.dst_node[i], dh = in.dst_host[i], sh = in.src_host[i];
+        if (a >= in.tn || b >= in.tn) {
+            bad |= 2;
+            continue;
+        }
+        if (dh >= in.num_hosts) {
+            bad |= 1;
+            continue;
+        }
+        const uint64_t s = in.send_ns[i];
+        // both table gathers are issued before the decision (each misses to HBM: one behind the other
+        // costs the pass a second round trip per event); a dropped event's latency is not used
+        const float loss = sx.loss ? sx.loss[(size_t)a * in.tn + b] : 0.0f;
+        const uint64_t delay = path_latency(sx.tab, a, b);
+        if (sx.loss && dropped(loss, sx.chance[i], sx.payload[i], s, sx.bootstrap_end)) {
+            status[i] = 0;
+            deliver[i] = ~0ull;
+            continue;
+        }
+        if (s > ~0ull - delay) {
+            bad |= 4;
+            continue;
+        }
+        uint64_t t = s + delay;
+        t = t < in.round_end ? in.round_end : t;
+        status[i] = 1;
+        deliver[i] = t;
+        ++sent;
+        const uint64_t id = in.event_id[i];
+        tmin = t < tmin ? t : tmin;
+        tmax = t > tmax ? t : tmax;
+        imin = id < imin ? id : imin;
+        imax = id > imax ? id : imax;
+        lmin = delay < lmin ? delay : lmin;
+        dmax = dh > dmax ? dh : dmax;
+        smax = sh > smax ? sh : smax;
+    }
+    for (int off = 32; off; off >>= 1) sent += __shfl_xor(sent, off, 64);
+    if ((threadIdx.x & 63) == 0 && sent) atomicAdd(&red->sent, (unsigned long long)sent);
+    ev_block_reduce(tmin, tmax, imin, imax, lmin, dmax, smax, bad, &red->r);
+}
+
+// increment_packet_count for a batch (mod.rs:449-456): counts[src_node, dst_node] += 1 per sent
+// event, saturating.  A round's packets share few node pairs (hosts share nodes), and same-address
+// atomics serialise at the memory side, so a wave first merges its equal pairs: the lanes are
+// grouped by 8 hashed bits of the pair (8 ballots, as the radix ranks), each group's first lane is
+// its leader, the lanes whose pair IS the leader's are counted and retired, and the leader adds the
+// count with one atomic.  Lanes that only shared the hash go round again (rare: 64 lanes over 256
+// hash values).  Saturation without a CAS loop: a 64-bit add whose returned old value shows a wrap
+// is followed by an atomic max to all-ones; whatever the interleaving, a counter that ever wrapped
+// ends at all-ones, because every add that wraps (from any intermediate value) issues its own max.
+// Runs after the prep pass's range checks passed: a * tn + b is inside counts.
+__global__ void __launch_bounds__(256) k_ev_counts(EvIn in, const uint8_t* __restrict__ status,
+                                                   unsigned long long* __restrict__ counts) {
+    const uint32_t lane = threadIdx.x & 63;
+    // whole waves stay in the loop together (the ballots below need every lane)
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i0 = blockIdx.x * (size_t)blockDim.x + (threadIdx.x & ~63u); i0 < in.n; i0 += stride) {
+        const size_t i = i0 + lane;
+        bool live = i < in.n && status[i];
+        const unsigned long long pair = live ? (unsigned long long)in.src_node[i] * in.tn + in.dst_node[i] : 0ull;
+        const uint32_t h = (uint32_t)((pair * 0x9E3779B97F4A7C15ull) >> 56);
+        while (__ballot(live)) {
+            unsigned long long m = __ballot(live);
+#pragma unroll
+            for (int b = 0; b < 8; ++b) {
+                const bool bit = (h >> b) & 1u;
+                const unsigned long long bb = __ballot(live && bit);
+                m &= bit ? bb : ~bb;
+            }
+            // m: the live lanes of my hash group (for a live lane it holds at least that lane)
+            const int leader = live ? __ffsll((long long)m) - 1 : (int)lane;
+            const unsigned long long lp = __shfl(pair, leader, 64);
+            const bool same = live && lp == pair;
+            const unsigned long long sm = __ballot(same);
+            if (live && (int)lane == leader) {
+                const unsigned long long c = (unsigned long long)__popcll(sm & m);
+                const unsigned long long old = atomicAdd(&counts[pair], c);
+                if (old + c < old) atomicMax(&counts[pair], ~0ull);
+            }
+            live = live && !same;
+        }
+    }
+}
+
 // Composite key layout: field f occupies bits [sh_f, sh_f + width_f) of the 128-bit (hi:lo) key.
 struct EvKeyFmt {
     uint32_t sh_src, sh_t, sh_dst;
@@ -160,16 +280,22 @@ __device__ __forceinline__ unsigned long long get_bits(unsigned long long lo, un
     return sh ? (lo >> sh) | (hi << (64 - sh)) : lo;
 }
 
-template <bool WIDE>
+// SEND: status[i] == 0 marks a dropped event; its key is host `num_hosts` (one past the last real
+// host: the parked run sorts behind every sent event) and nothing else
+template <bool WIDE, bool SEND = false>
 __global__ void __launch_bounds__(256) k_ev_keys(EvIn in, const uint64_t* __restrict__ deliver, EvKeyFmt f,
                                                  unsigned long long* __restrict__ klo, unsigned long long* __restrict__ khi,
-                                                 uint32_t* __restrict__ idx) {
+                                                 uint32_t* __restrict__ idx, const uint8_t* __restrict__ status = nullptr) {
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < in.n; i += (size_t)gridDim.x * blockDim.x) {
         unsigned long long lo = 0, hi = 0;
-        or_bits(lo, hi, in.event_id[i] - f.id_min, 0);
-        or_bits(lo, hi, in.src_host[i], f.sh_src);
-        or_bits(lo, hi, deliver[i] - f.t_min, f.sh_t);
-        or_bits(lo, hi, in.dst_host[i], f.sh_dst);
+        if (SEND && !status[i]) {
+            or_bits(lo, hi, in.num_hosts, f.sh_dst);
+        } else {
+            or_bits(lo, hi, in.event_id[i] - f.id_min, 0);
+            or_bits(lo, hi, in.src_host[i], f.sh_src);
+            or_bits(lo, hi, deliver[i] - f.t_min, f.sh_t);
+            or_bits(lo, hi, in.dst_host[i], f.sh_dst);
+        }
         klo[i] = lo;
         if (WIDE) khi[i] = hi;
         idx[i] = (uint32_t)i;
@@ -306,7 +432,9 @@ __global__ void __launch_bounds__(RS_THREADS) k_rs_scatter(const unsigned long l
 }
 
 // Sorted keys -> per-host offsets (empty hosts included) and the no-order check (equal keys).
-template <bool WIDE>
+// PARKED: keys of host `num_hosts` are a send batch's dropped events (all equal, never queued): they
+// are not checked, and host_off[num_hosts] = where their run starts = the number of sent events.
+template <bool WIDE, bool PARKED = false>
 __global__ void __launch_bounds__(256) k_ev_finish(const unsigned long long* __restrict__ klo,
                                                    const unsigned long long* __restrict__ khi, uint64_t n,
                                                    uint32_t sh_dst, uint32_t num_hosts, uint64_t* __restrict__ host_off,
@@ -318,7 +446,7 @@ __global__ void __launch_bounds__(256) k_ev_finish(const unsigned long long* __r
         if (i) {
             const unsigned long long plo = klo[i - 1], phi = WIDE ? khi[i - 1] : 0ull;
             h0 = (uint32_t)get_bits(plo, phi, sh_dst) + 1;
-            if (plo == lo && phi == hi) atomicOr(flags, 1u);
+            if (plo == lo && phi == hi && !(PARKED && d == num_hosts)) atomicOr(flags, 1u);
         }
         for (uint32_t h = h0; h <= d; ++h) host_off[h] = i;
         if (i == n - 1)

@@ -2267,17 +2267,22 @@ void direct_device(srg_ctx& c, const DevGraph& g, const uint32_t* nodes, uint32_
 // ---- stretch C5: packet-event batch (events.hip.h) ---------------------------------------
 inline uint32_t bit_width64(uint64_t v) { return v ? 64u - (uint32_t)__builtin_clzll(v) : 0u; }
 
+// status / n_order: a send batch with dropped events (status[i] == 0) -- they are parked behind host
+// num_hosts, and only the n_order sent indices in front of them reach out_order
 template <bool WIDE>
 void events_sort(srg_ctx& c, const EvIn& in, const uint64_t* deliver, const EvKeyFmt& f, uint32_t bits,
-                 uint32_t* out_order, uint64_t* host_off, hipStream_t st, uint32_t& passes) {
+                 uint32_t* out_order, uint64_t* host_off, hipStream_t st, uint32_t& passes,
+                 const uint8_t* status = nullptr, uint64_t n_order = ~0ull) {
     const uint64_t n = in.n;
+    if (!status) n_order = n;
     unsigned long long* k0 = (unsigned long long*)c.b_ek0.get(n * 8);
     unsigned long long* k1 = (unsigned long long*)c.b_ek1.get(n * 8);
     unsigned long long* h0 = WIDE ? (unsigned long long*)c.b_eh0.get(n * 8) : nullptr;
     unsigned long long* h1 = WIDE ? (unsigned long long*)c.b_eh1.get(n * 8) : nullptr;
     uint32_t* i0 = (uint32_t*)c.b_ei0.get(n * 4);
     uint32_t* i1 = (uint32_t*)c.b_ei1.get(n * 4);
-    k_ev_keys<WIDE><<<grid_for(n, 256 * 64), kThreads, 0, st>>>(in, deliver, f, k0, h0, i0);
+    if (status) k_ev_keys<WIDE, true><<<grid_for(n, 256 * 64), kThreads, 0, st>>>(in, deliver, f, k0, h0, i0, status);
+    else k_ev_keys<WIDE><<<grid_for(n, 256 * 64), kThreads, 0, st>>>(in, deliver, f, k0, h0, i0);
     const uint32_t ntiles = (uint32_t)((n + RS_TILE - 1) / RS_TILE);
     const int nh = (int)(256 * (size_t)ntiles);
     uint32_t* hist = (uint32_t*)c.b_ehist.get((size_t)nh * 4);
@@ -2298,8 +2303,12 @@ void events_sort(srg_ctx& c, const EvIn& in, const uint64_t* deliver, const EvKe
     HIP_CHECK(hipGetLastError());
     uint32_t* flag = (uint32_t*)c.b_red.get(64);
     HIP_CHECK(hipMemsetAsync(flag, 0, 4, st));
-    k_ev_finish<WIDE><<<grid_for(n, 256 * 64), kThreads, 0, st>>>(k0, h0, n, f.sh_dst, in.num_hosts, host_off, flag);
-    HIP_CHECK(hipMemcpyAsync(out_order, i0, n * 4, hipMemcpyDeviceToDevice, st));
+    if (status)
+        k_ev_finish<WIDE, true><<<grid_for(n, 256 * 64), kThreads, 0, st>>>(k0, h0, n, f.sh_dst, in.num_hosts, host_off,
+                                                                              flag);
+    else
+        k_ev_finish<WIDE><<<grid_for(n, 256 * 64), kThreads, 0, st>>>(k0, h0, n, f.sh_dst, in.num_hosts, host_off, flag);
+    HIP_CHECK(hipMemcpyAsync(out_order, i0, n_order * 4, hipMemcpyDeviceToDevice, st));
     uint32_t hflag = 0;
     HIP_CHECK(hipMemcpyAsync(&hflag, flag, 4, hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipStreamSynchronize(st));
@@ -2353,6 +2362,73 @@ void order_events_device(srg_ctx& c, const EvIn& in, uint64_t* deliver, uint32_t
         res->min_used_latency_ns = r.lat_min;
         res->key_bits = bits;
         res->radix_passes = passes;
+    }
+}
+
+// The whole per-packet tail of send_packet (srg_send_packets_device): order_events_device with the
+// drop decision in front, either table form, and the packet counters.
+void send_packets_device(srg_ctx& c, const EvIn& in, const EvSendIn& sx, uint8_t* status, uint64_t* deliver,
+                         uint32_t* out_order, uint64_t* host_off, unsigned long long* counts, hipStream_t st,
+                         srg_send_result* res) {
+    if (res) {
+        res->ev.min_next_event_ns = UINT64_MAX;
+        res->ev.min_used_latency_ns = UINT64_MAX;
+        res->ev.key_bits = 0;
+        res->ev.radix_passes = 0;
+        res->num_sent = res->num_dropped = 0;
+    }
+    HIP_CHECK(hipMemsetAsync(host_off, 0, ((size_t)in.num_hosts + 1) * 8, st));
+    if (in.n == 0) {
+        HIP_CHECK(hipStreamSynchronize(st));
+        return;
+    }
+    if (in.n >= 0xFFFFFFFFull) fail(SRG_ERR_ARG, "event batch too large (>= 2^32 events)");
+    if (in.num_hosts == UINT32_MAX) fail(SRG_ERR_ARG, "num_hosts too large (host 2^32 - 1 parks the dropped events)");
+    EvSendReduce* red = (EvSendReduce*)c.b_ered.get(sizeof(EvSendReduce));
+    EvSendReduce init{{~0ull, 0ull, ~0ull, 0ull, ~0ull, 0u, 0u, 0u, 0u}, 0ull};
+    HIP_CHECK(hipMemcpyAsync(red, &init, sizeof(EvSendReduce), hipMemcpyHostToDevice, st));
+    k_ev_send_prep<<<grid_for(in.n, 2048), kThreads, 0, st>>>(in, sx, status, deliver, red);
+    HIP_CHECK(hipGetLastError());
+    EvSendReduce sr;
+    HIP_CHECK(hipMemcpyAsync(&sr, red, sizeof(EvSendReduce), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    const EvReduce& r = sr.r;
+    if (r.bad & 2) fail(SRG_ERR_ARG, "event node position out of range (>= table n)");
+    if (r.bad & 1) fail(SRG_ERR_ARG, "event dst_host out of range (>= num_hosts)");
+    if (r.bad & 4) fail(SRG_ERR_LATENCY_RANGE, "deliver time overflows EmulatedTime (send + latency)");
+    const uint64_t sent = sr.sent, drops = in.n - sent;
+    // the counters move once the range checks passed (every index is inside the table), as
+    // increment_packet_count runs at the send, before any queue is popped
+    if (counts && sent) {
+        k_ev_counts<<<grid_for(in.n, 2048), kThreads, 0, st>>>(in, status, counts);
+        HIP_CHECK(hipGetLastError());
+    }
+    uint32_t bits = 0, passes = 0;
+    if (sent) {
+        EvKeyFmt f{};
+        // dropped events are parked behind host num_hosts: the host field must hold that value
+        const uint32_t b_id = bit_width64(r.id_max - r.id_min), b_src = bit_width64(r.src_max),
+                       b_t = bit_width64(r.t_max - r.t_min), b_dst = bit_width64(drops ? in.num_hosts : r.dst_max);
+        f.t_min = r.t_min;
+        f.id_min = r.id_min;
+        f.sh_src = b_id;
+        f.sh_t = b_id + b_src;
+        f.sh_dst = b_id + b_src + b_t;
+        bits = f.sh_dst + b_dst;
+        if (bits > 128) fail(SRG_ERR_ARG, "event batch key wider than 128 bits");
+        const uint8_t* parked = drops ? status : nullptr;
+        if (bits <= 64) events_sort<false>(c, in, deliver, f, bits, out_order, host_off, st, passes, parked, sent);
+        else events_sort<true>(c, in, deliver, f, bits, out_order, host_off, st, passes, parked, sent);
+    } else {
+        HIP_CHECK(hipStreamSynchronize(st));
+    }
+    if (res) {
+        res->ev.min_next_event_ns = r.t_min;
+        res->ev.min_used_latency_ns = r.lat_min;
+        res->ev.key_bits = bits;
+        res->ev.radix_passes = passes;
+        res->num_sent = sent;
+        res->num_dropped = drops;
     }
 }
 
@@ -3805,6 +3881,47 @@ int srg_order_packet_events_device(srg_ctx* ctx, const srg_event_batch* b, const
         order_events_device(*ctx, in, out_deliver, out_order, out_host_off, st, res);
         HIP_CHECK(hipStreamSynchronize(st));
         if (res) res->ms_total = ms_since(t0);
+    });
+}
+
+int srg_send_packets_device(srg_ctx* ctx, const srg_send_batch* sb, const srg_path_table_dev* t, uint8_t* out_status,
+                            uint64_t* out_deliver, uint32_t* out_order, uint64_t* out_host_off, uint64_t* packet_counts,
+                            void* hip_stream, srg_send_result* res, char* errbuf, size_t errlen) {
+    if (!ctx || !sb || !t || !out_host_off) {
+        set_err(errbuf, errlen, "null argument");
+        return SRG_ERR_ARG;
+    }
+    const srg_event_batch* b = &sb->ev;
+    if (b->num_events && (!out_status || !out_deliver || !out_order || !b->src_node || !b->dst_node || !b->src_host ||
+                          !b->dst_host || !b->send_time_ns || !b->src_event_id)) {
+        set_err(errbuf, errlen, "null argument");
+        return SRG_ERR_ARG;
+    }
+    if (!t->latency_ns == !t->latency_key) {
+        set_err(errbuf, errlen, "path table: exactly one of latency_ns and latency_key must be given");
+        return SRG_ERR_ARG;
+    }
+    if (t->latency_key && (!t->diag_ns || t->unit_ns < 1)) {
+        set_err(errbuf, errlen, "path table: latency_key needs diag_ns and unit_ns >= 1");
+        return SRG_ERR_ARG;
+    }
+    if (t->packet_loss && b->num_events && (!sb->chance || !sb->payload_size)) {
+        set_err(errbuf, errlen, "send batch: chance and payload_size are required with a packet_loss table");
+        return SRG_ERR_ARG;
+    }
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    return guard(errbuf, errlen, [&]() {
+        auto t0 = std::chrono::steady_clock::now();
+        HIP_CHECK(hipSetDevice(ctx->device));
+        hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+        EvIn in{b->num_events, b->src_node, b->dst_node, b->src_host, b->dst_host, b->send_time_ns,
+                b->src_event_id, nullptr, t->n, b->num_hosts, b->round_end_ns};
+        EvSendIn sx{{t->latency_ns, t->latency_key, t->diag_ns, t->unit_ns, t->n}, t->packet_loss, sb->chance,
+                    sb->payload_size, sb->bootstrap_end_ns};
+        send_packets_device(*ctx, in, sx, out_status, out_deliver, out_order, out_host_off,
+                            (unsigned long long*)packet_counts, st, res);
+        HIP_CHECK(hipStreamSynchronize(st));
+        if (res) res->ev.ms_total = ms_since(t0);
     });
 }
 

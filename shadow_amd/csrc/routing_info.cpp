@@ -334,4 +334,30 @@ void srg_routing_info_tables(const srg_routing_info* ri, const uint64_t** latenc
     if (n) *n = ri ? ri->n : 0;
 }
 
+int srg_routing_info_key_tables(const srg_routing_info* ri, const uint32_t** key, const uint64_t** diag_ns,
+                                uint64_t* unit_ns, const float** packet_loss, uint32_t* n) {
+    if (!ri || !ri->key) return 0;
+    if (key) *key = ri->key;
+    if (diag_ns) *diag_ns = ri->diag.data();
+    if (unit_ns) *unit_ns = ri->unit;
+    if (packet_loss) *packet_loss = ri->loss;
+    if (n) *n = ri->n;
+    return 1;
+}
+
+void srg_routing_info_add_packet_counts(srg_routing_info* ri, const uint64_t* counts) {
+    if (!ri || !counts) return;
+    for (uint32_t a = 0; a < ri->n; ++a) {
+        const uint64_t* row = counts + (size_t)a * ri->n;
+        for (uint32_t b = 0; b < ri->n; ++b) {
+            if (!row[b]) continue;
+            const uint64_t k = Counters::key(ri->ids[a], ri->ids[b]);
+            auto& s = ri->counters.of(k);
+            std::lock_guard<std::mutex> lk(s.mu);
+            uint64_t& c = s.m[k];
+            c = row[b] > UINT64_MAX - c ? UINT64_MAX : c + row[b];  // saturating_add
+        }
+    }
+}
+
 }  // extern "C"

@@ -10,6 +10,11 @@ include/shadow_routing.h):
   min next event           manager.rs:459-464
 The latency table is the dense routing table (RoutingInfo's backing store), e.g. the
 `latency_ns` matrix of a PathTable, kept in HBM.  torch tensors are only HBM containers here.
+
+send_packets / send_packets_device (srg_send_packets_device) start higher up, at the drop decision
+(worker.rs:374-390: chance >= 1.0f32 - packet_loss, payload > 0, not bootstrapping), take the
+table in either form a RoutingInfo keeps (DevicePathTable), and count the sent packets per node
+pair (increment_packet_count, worker.rs:395).  Only the RNG draw stays with the caller: `chance`.
 """
 import ctypes
 
@@ -87,9 +92,114 @@ def order_packet_events(router, batch, table, num_hosts, round_end_ns, device=No
             off.cpu().numpy().view(np.uint64), res)
 
 
-def synthetic_round(n, num_hosts, table_n, seed=7, t0=10**12, runahead=5_000_000):
+class DeviceSendBatch(DeviceEventBatch):
+    """A DeviceEventBatch plus what the drop decision reads: batch["chance"] f64 [n] (the host's
+    draws, program order) and batch["payload_size"] u32 [n]; both may be absent when the table has
+    no packet_loss."""
+
+    def __init__(self, batch, num_hosts, round_end_ns, bootstrap_end_ns=0, device="cuda:0"):
+        super().__init__(batch, num_hosts, round_end_ns, device)
+        dev = torch.device(device)
+        self.bootstrap_end_ns = int(bootstrap_end_ns)
+        self.chance = self.payload = None
+        if batch.get("chance") is not None:
+            self.chance = torch.from_numpy(np.ascontiguousarray(batch["chance"], dtype=np.float64)).to(dev)
+        if batch.get("payload_size") is not None:
+            self.payload = _i32(batch["payload_size"], dev)
+
+    def as_send_struct(self):
+        return N.SendBatch(self.as_struct(), self.chance.data_ptr() if self.chance is not None else None,
+                           self.payload.data_ptr() if self.payload is not None else None, self.bootstrap_end_ns)
+
+
+class DevicePathTable:
+    """A routing table resident in HBM, by node position, in either form (srg_path_table_dev):
+    u64 latencies, or u32 keys + the diagonal's raw latencies + the unit; packet_loss optional."""
+
+    def __init__(self, n, latency_ns=None, key=None, diag=None, unit=1, packet_loss=None):
+        self.n, self.unit = int(n), int(unit)
+        self.latency_ns, self.key, self.diag, self.packet_loss = latency_ns, key, diag, packet_loss
+
+    @classmethod
+    def from_arrays(cls, latency_ns=None, key=None, diag=None, unit=1, packet_loss=None, device="cuda:0"):
+        dev = torch.device(device)
+        first = latency_ns if latency_ns is not None else key
+        if first is None:
+            raise ValueError("latency_ns or key is required")
+        return cls(np.asarray(first).shape[0],
+                   _i64(np.asarray(latency_ns), dev) if latency_ns is not None else None,
+                   _i32(np.asarray(key), dev) if key is not None else None,
+                   _i64(np.asarray(diag), dev) if diag is not None else None, unit,
+                   torch.from_numpy(np.ascontiguousarray(packet_loss, dtype=np.float32)).to(dev)
+                   if packet_loss is not None else None)
+
+    @classmethod
+    def from_routing_info(cls, ri, device="cuda:0"):
+        """Uploads the u32 keys when the RoutingInfo kept them (no u64 widening on the host), else u64."""
+        kt = ri.key_tables()
+        if kt is not None:
+            key, diag, unit, loss = kt
+            return cls.from_arrays(key=key, diag=diag, unit=unit, packet_loss=loss, device=device)
+        lat, loss, _ = ri.tables()
+        return cls.from_arrays(latency_ns=lat, packet_loss=loss, device=device)
+
+    def as_struct(self):
+        def ptr(t):
+            return t.data_ptr() if t is not None else None
+        return N.PathTableDev(self.n, 0, ptr(self.latency_ns), ptr(self.key), ptr(self.diag), self.unit,
+                              ptr(self.packet_loss))
+
+
+def send_packets_device(router, dbatch, table, out_status_t, out_deliver_t, out_order_t, out_host_off_t, counts_t=None,
+                        stream=None):
+    """dbatch: DeviceSendBatch; table: DevicePathTable; outputs uint8[n], int64[n], int32[n] (the first
+    num_sent entries are written), int64[num_hosts + 1]; counts_t: int64 [tn, tn] accumulated in place."""
+    assert out_status_t.dtype == torch.uint8 and out_status_t.numel() == dbatch.n
+    assert out_deliver_t.numel() == dbatch.n and out_order_t.numel() == dbatch.n
+    assert out_host_off_t.numel() == dbatch.num_hosts + 1
+    assert counts_t is None or (counts_t.dtype == torch.int64 and counts_t.numel() == table.n * table.n
+                                and counts_t.is_contiguous())
+    res = N.SendResult()
+    err = ctypes.create_string_buffer(1024)
+    b, t = dbatch.as_send_struct(), table.as_struct()
+    s = stream if stream is not None else torch.cuda.current_stream(out_host_off_t.device)
+    rc = N.lib().srg_send_packets_device(
+        router._h, ctypes.byref(b), ctypes.byref(t), out_status_t.data_ptr(), out_deliver_t.data_ptr(),
+        out_order_t.data_ptr(), out_host_off_t.data_ptr(), counts_t.data_ptr() if counts_t is not None else None,
+        ctypes.c_void_p(s.cuda_stream), ctypes.byref(res), err, len(err))
+    if rc == N.SRG_ERR_EVENT_ORDER:
+        raise EventOrderError(rc, err.value.decode(errors="replace"))
+    if rc != N.SRG_OK:
+        _raise(rc, err.value.decode(errors="replace"))
+    return res.as_dict()
+
+
+def send_packets(router, batch, table, num_hosts, round_end_ns, bootstrap_end_ns=0, counts=None, device=None):
+    """Host arrays in, host arrays out: (status u8[n], deliver u64[n], order u32[num_sent],
+    host_offsets u64[H+1], result).  table: a DevicePathTable; counts: a persistent int64 [tn, tn]
+    tensor on the device that accumulates the packet counts (None = not counted)."""
+    dev = torch.device(device or f"cuda:{router.device}")
+    db = DeviceSendBatch(batch, num_hosts, round_end_ns, bootstrap_end_ns, dev)
+    n = db.n
+    status = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)[:n]
+    deliver = torch.empty(max(n, 1), dtype=torch.int64, device=dev)[:n]
+    order = torch.empty(max(n, 1), dtype=torch.int32, device=dev)[:n]
+    off = torch.empty(db.num_hosts + 1, dtype=torch.int64, device=dev)
+    res = send_packets_device(router, db, table, status, deliver, order, off, counts)
+    torch.cuda.synchronize(dev)
+    return (status.cpu().numpy(), deliver.cpu().numpy().view(np.uint64),
+            order[:res["num_sent"]].cpu().numpy().view(np.uint32), off.cpu().numpy().view(np.uint64), res)
+
+
+def synthetic_round(n, num_hosts, table_n, seed=7, t0=10**12, runahead=5_000_000, loss=None, zero_payload=0.1):
     """n events, send times uniform in one round window [t0, t0 + runahead),
-    src/dst hosts uniform, per-source monotone event ids, hosts mapped to table rows."""
+    src/dst hosts uniform, per-source monotone event ids, hosts mapped to table rows.
+
+    loss (a mean drop probability in [0, 0.5], default None = as before): the batch also gets what
+    send_packets reads -- "chance" (f64 uniform in [0, 1), one draw per packet) and "payload_size"
+    (u32, a `zero_payload` share of them 0: bare ACKs) -- and a third value is returned, the
+    packet_loss table f32 [table_n, table_n], uniform in [0, 2 loss).  These come from a generator
+    of their own, so the six base arrays are the same with and without."""
     rng = np.random.default_rng(seed)
     src_host = rng.integers(0, num_hosts, n, dtype=np.uint32)
     dst_host = rng.integers(0, num_hosts, n, dtype=np.uint32)
@@ -101,5 +211,12 @@ def synthetic_round(n, num_hosts, table_n, seed=7, t0=10**12, runahead=5_000_000
     starts = np.r_[0, np.flatnonzero(np.diff(src_host[order])) + 1]
     counts = np.diff(np.r_[starts, n])
     eid[order] = (np.arange(n) - np.repeat(starts, counts)).astype(np.uint64) + 1
-    return dict(src_node=host_node[src_host], dst_node=host_node[dst_host], src_host=src_host, dst_host=dst_host,
-                send_time_ns=send, src_event_id=eid), t0 + runahead
+    batch = dict(src_node=host_node[src_host], dst_node=host_node[dst_host], src_host=src_host, dst_host=dst_host,
+                 send_time_ns=send, src_event_id=eid)
+    if loss is None:
+        return batch, t0 + runahead
+    rng2 = np.random.default_rng([seed, 0x5E9D])
+    batch["chance"] = rng2.random(n)
+    batch["payload_size"] = np.where(rng2.random(n) < zero_payload, 0, rng2.integers(1, 1461, n)).astype(np.uint32)
+    table = (rng2.random((table_n, table_n), dtype=np.float32) * np.float32(2.0 * loss)).astype(np.float32)
+    return batch, t0 + runahead, table

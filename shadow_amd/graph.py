@@ -453,6 +453,37 @@ class RoutingInfo:
 
         return (view(lp, ctypes.c_uint64, (n, n)), view(fp, ctypes.c_float, (n, n)), view(ip, ctypes.c_uint32, (n,)))
 
+    def key_tables(self):
+        """(key u32 [n, n], diag_ns u64 [n], unit_ns, packet_loss f32 [n, n]) when the table kept the
+        build's u32 latency keys (latency = key * unit_ns off the diagonal, diag_ns on it), else None
+        (a u64 table: use tables()).  Zero-copy views like tables(); never builds the u64 view."""
+        kp, dp, fp, unit, n = N._u32p(), N._u64p(), N._f32p(), ctypes.c_uint64(), ctypes.c_uint32()
+        if not N.lib().srg_routing_info_key_tables(self._h, ctypes.byref(kp), ctypes.byref(dp), ctypes.byref(unit),
+                                                   ctypes.byref(fp), ctypes.byref(n)):
+            return None
+        n = n.value
+        if n == 0:
+            return (np.zeros((0, 0), np.uint32), np.zeros(0, np.uint64), int(unit.value), np.zeros((0, 0), np.float32))
+
+        def view(ptr, ctype, shape):
+            buf = (ctype * int(np.prod(shape))).from_address(ctypes.addressof(ptr.contents))
+            buf._owner = self
+            return np.ctypeslib.as_array(buf).reshape(shape)
+
+        return (view(kp, ctypes.c_uint32, (n, n)), view(dp, ctypes.c_uint64, (n,)), int(unit.value),
+                view(fp, ctypes.c_float, (n, n)))
+
+    def add_packet_counts(self, counts):
+        """Merge a send batch's counter table (u64 [n, n] by node position, events.send_packets) into
+        the counters behind increment_packet_count / packet_count (saturating)."""
+        n = int(N.lib().srg_routing_info_num_nodes(self._h))
+        if hasattr(counts, "cpu"):  # an int64 tensor holding the u64 counters
+            counts = counts.cpu().numpy().view(np.uint64)
+        c = np.ascontiguousarray(counts, dtype=np.uint64)
+        if c.size != n * n:
+            raise ValueError(f"counts must hold {n} x {n} entries")
+        N.lib().srg_routing_info_add_packet_counts(self._h, c.ctypes.data)
+
     def __len__(self):
         return int(N.lib().srg_routing_info_num_nodes(self._h)) ** 2
 
