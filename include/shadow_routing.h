@@ -473,6 +473,70 @@ int srg_routing_info_key_tables(const srg_routing_info* ri, const uint32_t** key
  * under the GML ids of its positions.  Thread-safe against the per-packet calls.                */
 void srg_routing_info_add_packet_counts(srg_routing_info* ri, const uint64_t* counts_by_position /* host, n*n */);
 
+/* ---- device-resident per-host packet-event queues, across rounds ------------------------
+ * The two batch entries above order one round's sends in isolation; these keep the per-host
+ * EventQueues themselves (event_queue.rs:10-55) in HBM: a round's sent events are merged in at the
+ * barrier, a window's events are popped out in the reference's order.  Packet events only: Local
+ * events (and the CPU-delay re-push, host.rs:841-843) stay with the host, which interleaves its
+ * popped packet slice with its local heap by (time, Packet before Local) (event.rs:103-110).
+ *   one queue per destination host; total order (time, src_host_id, src_host_event_id)
+ *   push of two events of one host equal in all three, one of them possibly resident:
+ *        SRG_ERR_EVENT_ORDER
+ *   push of an event with time < its host's last popped time (assert!, event_queue.rs:33):
+ *        SRG_ERR_TIME_BACKWARD; time == last popped is accepted
+ *   pop(until) removes, per host, exactly the events with time < until (Host::execute,
+ *        host.rs:809-818) and sets the host's last popped time to the largest popped time
+ *   min_next_event_ns after either call = the minimum head time over all hosts (UINT64_MAX when
+ *        everything is empty): the manager's min_next_event_time (manager.rs:416-435, 459-464)
+ * Any call that returns an error leaves the queues exactly as they were.  Both calls return after
+ * their stream work is complete.  Cost: push O(backlog + batch) (a merge, never a re-sort); pop
+ * O(popped + num_hosts), the kept backlog is not rewritten.                                     */
+#define SRG_ERR_TIME_BACKWARD 12
+/* opaque; lives in the HBM of ctx's device; not thread-safe; destroy it before its ctx */
+typedef struct srg_event_queues srg_event_queues;
+/* reserve_events: capacity allocated up front; growth past it reallocates geometrically and keeps
+ * the contents (a failed allocation is SRG_ERR_OOM with the queues unchanged) */
+int srg_event_queues_create(srg_ctx* ctx, uint32_t num_hosts, uint64_t reserve_events, srg_event_queues** out,
+                            char* errbuf, size_t errlen);
+void srg_event_queues_destroy(srg_event_queues* q);
+/* merged outputs per merge workgroup (the tests place events around its multiples) */
+uint32_t srg_event_queues_merge_tile(void);
+
+typedef struct srg_queue_result {
+    uint64_t num_moved;          /* pushed / popped by this call (pop: the count needed when capacity was short) */
+    uint64_t num_queued;         /* live events after the call */
+    uint64_t min_next_event_ns;  /* min head over hosts after the call */
+    double ms_total;
+} srg_queue_result;
+
+/* batch_dev, deliver_ns_dev, order_dev[num_order]: exactly what srg_order_packet_events_device
+ * (num_order = num_events) or srg_send_packets_device (num_order = num_sent) took and wrote.
+ * tag_dev[num_events]: the caller's opaque u64 per event (the packet handle); NULL = the event's
+ * index.  Validated on the device: order[i] < num_events, dst_host < the queues' num_hosts, and the
+ * gathered keys strictly increase under (dst_host, time, src_host, event_id); otherwise
+ * SRG_ERR_ARG ("order is not the batch's queue order").                                          */
+int srg_event_queues_push_device(srg_event_queues* q, const srg_event_batch* batch_dev,
+                                 const uint64_t* deliver_ns_dev, const uint32_t* order_dev, uint64_t num_order,
+                                 const uint64_t* tag_dev, void* hip_stream, srg_queue_result* result, char* errbuf,
+                                 size_t errlen);
+
+/* Popped events grouped by host (increasing HostId), each host's in pop order;
+ * out_host_offsets_dev[num_hosts + 1].  out_src_host_dev / out_src_event_id_dev may be NULL; with
+ * out_capacity 0 every output may be NULL (a sizing call).  More than out_capacity events due:
+ * SRG_ERR_ARG, num_moved = the count needed, nothing popped.                                     */
+int srg_event_queues_pop_device(srg_event_queues* q, uint64_t until_ns, uint64_t out_capacity,
+                                uint64_t* out_time_ns_dev, uint32_t* out_src_host_dev, uint64_t* out_src_event_id_dev,
+                                uint64_t* out_tag_dev, uint64_t* out_host_offsets_dev, void* hip_stream,
+                                srg_queue_result* result, char* errbuf, size_t errlen);
+
+/* The controller's window step (controller.rs:88-112): start = min_next_event_ns; end =
+ * min(start + runahead_ns (saturating at UINT64_MAX), end_time_ns).  Returns 1 and the window when
+ * start < end, 0 when the simulation is over.  A usage error -- runahead_ns == 0 (the reference's
+ * assert_ne!) or a null output -- returns -SRG_ERR_ARG: negative, because 1 already means "a
+ * window".  No GPU work.                                                                        */
+int srg_next_window(uint64_t min_next_event_ns, uint64_t runahead_ns, uint64_t end_time_ns,
+                    uint64_t* window_start_ns, uint64_t* window_end_ns);
+
 /* Library build/version string. */
 const char* srg_version(void);
 

@@ -22,6 +22,7 @@ SRG_ERR_PARSE = 8
 SRG_ERR_RCCL = 9
 SRG_ERR_INTERNAL = 10
 SRG_ERR_EVENT_ORDER = 11
+SRG_ERR_TIME_BACKWARD = 12
 
 SRG_PATH_DENSE_U32 = 0
 SRG_PATH_DENSE_U64 = 1
@@ -146,6 +147,18 @@ class SendResult(ctypes.Structure):
         return d
 
 
+class QueueResult(ctypes.Structure):
+    _fields_ = [
+        ("num_moved", ctypes.c_uint64),
+        ("num_queued", ctypes.c_uint64),
+        ("min_next_event_ns", ctypes.c_uint64),
+        ("ms_total", ctypes.c_double),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class Stats(ctypes.Structure):
     _fields_ = [
         ("ms_total", ctypes.c_double),
@@ -199,6 +212,8 @@ EXPORTS = [
     "srg_multi_create", "srg_multi_destroy", "srg_multi_size", "srg_multi_set_option", "srg_multi_compute_shortest_paths",
     "srg_multi_get_direct_paths", "srg_routing_info_build_multi", "srg_get_option",
     "srg_send_packets_device", "srg_routing_info_key_tables", "srg_routing_info_add_packet_counts",
+    "srg_event_queues_create", "srg_event_queues_destroy", "srg_event_queues_merge_tile",
+    "srg_event_queues_push_device", "srg_event_queues_pop_device", "srg_next_window",
 ]
 
 _lib = None
@@ -287,6 +302,23 @@ def lib():
                                               c.POINTER(c.c_uint32)]
     L.srg_routing_info_add_packet_counts.restype = None
     L.srg_routing_info_add_packet_counts.argtypes = [c.c_void_p, c.c_void_p]
+    L.srg_event_queues_create.restype = c.c_int
+    L.srg_event_queues_create.argtypes = [c.c_void_p, c.c_uint32, c.c_uint64, c.POINTER(c.c_void_p), c.c_char_p,
+                                          c.c_size_t]
+    L.srg_event_queues_destroy.restype = None
+    L.srg_event_queues_destroy.argtypes = [c.c_void_p]
+    L.srg_event_queues_merge_tile.restype = c.c_uint32
+    L.srg_event_queues_merge_tile.argtypes = []
+    L.srg_event_queues_push_device.restype = c.c_int
+    L.srg_event_queues_push_device.argtypes = [
+        c.c_void_p, c.POINTER(EventBatch), c.c_void_p, c.c_void_p, c.c_uint64, c.c_void_p, c.c_void_p,
+        c.POINTER(QueueResult), c.c_char_p, c.c_size_t]
+    L.srg_event_queues_pop_device.restype = c.c_int
+    L.srg_event_queues_pop_device.argtypes = [
+        c.c_void_p, c.c_uint64, c.c_uint64, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p,
+        c.POINTER(QueueResult), c.c_char_p, c.c_size_t]
+    L.srg_next_window.restype = c.c_int
+    L.srg_next_window.argtypes = [c.c_uint64, c.c_uint64, c.c_uint64, _u64p, _u64p]
     L.srg_routing_info_build.restype = c.c_int
     L.srg_routing_info_build.argtypes = [c.c_void_p, c.POINTER(EdgeList), c.c_void_p, c.c_uint32, c.c_int,
                                          c.POINTER(c.c_void_p), c.POINTER(Stats), c.c_char_p, c.c_size_t]

@@ -53,6 +53,7 @@
 #include "sparse.hip.h"
 #include "sparse_ds.hip.h"
 #include "events.hip.h"
+#include "event_queue.hip.h"
 #include "xchg.hip.h"
 
 #include <hipcub/hipcub.hpp>
@@ -2432,6 +2433,155 @@ void send_packets_device(srg_ctx& c, const EvIn& in, const EvSendIn& sx, uint8_t
     }
 }
 
+}  // namespace
+
+// ---- device-resident per-host event queues (event_queue.hip.h) ---------------------------
+// Two sets of resident arrays: `cur` is the queues, the other one is where a push builds the
+// merged result; it becomes `cur` only after the device flags were read (an error leaves the
+// queues as they were).  A set that is too small is simply reallocated before it is built into:
+// the contents live in the other one.
+struct srg_event_queues {
+    srg_ctx* ctx = nullptr;
+    uint32_t num_hosts = 0;
+    struct Set {
+        DevBuf k0, k1, k2, tag, host_off, head;
+        uint64_t cap = 0;
+        EvqSet ptrs() const { return EvqSet{(uint64_t*)k0.p, (uint64_t*)k1.p, (uint64_t*)k2.p, (uint64_t*)tag.p}; }
+        void reserve(uint64_t n) {
+            if (n <= cap) return;
+            const uint64_t want = std::max(n, 2 * cap);
+            cap = 0;  // (a failed allocation leaves the set empty, not half grown)
+            for (DevBuf* b : {&k0, &k1, &k2, &tag}) b->get(want * 8);
+            cap = want;
+        }
+    } set[2];
+    int cur = 0;
+    DevBuf last_popped, bk0, bk1, bk2, btag, dead, dead_excl, part_a, part_live, new_head, cnt, offs, state, scantmp;
+    uint64_t stored = 0;  // events in the current set's arrays, popped ones included
+    uint64_t live = 0;
+    uint64_t min_next = UINT64_MAX;
+};
+
+namespace {
+
+void evq_fill_result(const srg_event_queues& q, uint64_t moved, srg_queue_result* res) {
+    if (!res) return;
+    res->num_moved = moved;
+    res->num_queued = q.live;
+    res->min_next_event_ns = q.min_next;
+}
+
+void evq_scan(srg_event_queues& q, const uint64_t* in, uint64_t* out, hipStream_t st) {
+    const int n = (int)q.num_hosts + 1;
+    size_t tb = 0;
+    HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, in, out, n, st));
+    void* tmp = q.scantmp.get(tb);
+    HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(tmp, tb, in, out, n, st));
+}
+
+EvqState evq_read_state(EvqState* dev, hipStream_t st) {
+    EvqState s;
+    HIP_CHECK(hipMemcpyAsync(&s, dev, sizeof(EvqState), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    return s;
+}
+
+void evq_push(srg_event_queues& q, const srg_event_batch* b, const uint64_t* deliver, const uint32_t* order,
+              uint64_t nb, const uint64_t* tag, hipStream_t st, srg_queue_result* res) {
+    evq_fill_result(q, 0, res);
+    if (nb == 0) return;  // nothing to merge: the queues (their popped prefixes too) stay as they are
+    if (nb > b->num_events) fail(SRG_ERR_ARG, "num_order exceeds the batch's num_events");
+    if (b->num_events >= 0xFFFFFFFFull) fail(SRG_ERR_ARG, "event batch too large (>= 2^32 events)");
+    const uint32_t H = q.num_hosts;
+    srg_event_queues::Set& A = q.set[q.cur];
+    srg_event_queues::Set& O = q.set[q.cur ^ 1];
+    const EvqSet B{(uint64_t*)q.bk0.get(nb * 8), (uint64_t*)q.bk1.get(nb * 8), (uint64_t*)q.bk2.get(nb * 8),
+                   (uint64_t*)q.btag.get(nb * 8)};
+    EvqState* ds = (EvqState*)q.state.get(sizeof(EvqState));
+    const EvqState init{~0ull, 0u, 0u};
+    HIP_CHECK(hipMemcpyAsync(ds, &init, sizeof(EvqState), hipMemcpyHostToDevice, st));
+    const EvqGatherIn gi{b->num_events, nb, order, b->dst_host, b->src_host, b->src_event_id, deliver, tag, H};
+    k_evq_gather<<<grid_for(nb, 2048), kThreads, 0, st>>>(gi, B, (const uint64_t*)q.last_popped.p, ds);
+    HIP_CHECK(hipGetLastError());
+    EvqState s = evq_read_state(ds, st);
+    if (s.flags & EVQ_BAD_ORDER)
+        fail(SRG_ERR_ARG,
+             "order is not the batch's queue order (an entry >= num_events, a dst_host >= num_hosts, or keys "
+             "not strictly increasing by dst_host, time, src_host, event id)");
+    if (s.flags & EVQ_TIME_BACKWARD)
+        fail(SRG_ERR_TIME_BACKWARD,
+             "assertion failed: event.time() >= self.last_popped_event_time: a pushed event is earlier than "
+             "its host's last popped event");
+    const uint64_t n_out = q.live + nb, n = q.stored + nb;
+    O.reserve(n_out);
+    const uint64_t* a_off = (const uint64_t*)A.host_off.p;
+    const uint64_t* a_head = (const uint64_t*)A.head.p;
+    uint64_t* dead = (uint64_t*)q.dead.p;
+    uint64_t* dead_excl = (uint64_t*)q.dead_excl.p;
+    k_evq_dead<<<grid_for((size_t)H + 1), kThreads, 0, st>>>(a_off, a_head, H, dead);
+    evq_scan(q, dead, dead_excl, st);
+    const uint64_t ntiles = (n + EVQ_TILE - 1) / EVQ_TILE;
+    if (ntiles >= 0x7FFFFFFFull) fail(SRG_ERR_ARG, "event queues too large for one merge launch");
+    uint64_t* part_a = (uint64_t*)q.part_a.get((ntiles + 1) * 8);
+    uint64_t* part_live = (uint64_t*)q.part_live.get((ntiles + 1) * 8);
+    k_evq_partition<<<grid_for(ntiles + 1), kThreads, 0, st>>>(A.ptrs(), q.stored, B, nb, a_off, a_head, dead_excl, H,
+                                                                ntiles, part_a, part_live);
+    k_evq_merge<<<(unsigned)ntiles, EVQ_THREADS, 0, st>>>(A.ptrs(), B, n, part_a, part_live, a_head, O.ptrs(), n_out, ds);
+    k_evq_finish<<<grid_for(n_out, 2048), kThreads, 0, st>>>((const uint64_t*)O.k0.p, n_out, H, (uint64_t*)O.host_off.p,
+                                                             (uint64_t*)O.head.p);
+    k_evq_min<<<grid_for(H, 2048), kThreads, 0, st>>>(O.ptrs(), (const uint64_t*)O.host_off.p,
+                                                      (const uint64_t*)O.head.p, H, ds);
+    HIP_CHECK(hipGetLastError());
+    s = evq_read_state(ds, st);
+    if (s.flags & EVQ_EQUAL_KEYS)
+        fail(SRG_ERR_EVENT_ORDER,
+             "called `Option::unwrap()` on a `None` value: two packet events with equal (time, src_host_id, "
+             "src_host_event_id) have no relative order");
+    q.cur ^= 1;
+    q.stored = q.live = n_out;
+    q.min_next = s.min_head;
+    evq_fill_result(q, nb, res);
+}
+
+void evq_pop(srg_event_queues& q, uint64_t until, uint64_t capacity, uint64_t* out_time, uint32_t* out_src,
+             uint64_t* out_id, uint64_t* out_tag, uint64_t* out_off, hipStream_t st, srg_queue_result* res) {
+    evq_fill_result(q, 0, res);
+    const uint32_t H = q.num_hosts;
+    srg_event_queues::Set& A = q.set[q.cur];
+    uint64_t* host_off = (uint64_t*)A.host_off.p;
+    uint64_t* head = (uint64_t*)A.head.p;
+    uint64_t* new_head = (uint64_t*)q.new_head.p;
+    uint64_t* cnt = (uint64_t*)q.cnt.p;
+    uint64_t* offs = (uint64_t*)q.offs.p;
+    k_evq_pop_find<<<grid_for((size_t)H + 1, 2048), kThreads, 0, st>>>(A.ptrs(), host_off, head, H, until, new_head, cnt);
+    HIP_CHECK(hipGetLastError());
+    evq_scan(q, cnt, offs, st);
+    uint64_t total = 0;
+    HIP_CHECK(hipMemcpyAsync(&total, offs + H, 8, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    if (total > capacity) {
+        if (res) res->num_moved = total;
+        fail(SRG_ERR_ARG, "out_capacity too small: " + std::to_string(total) + " events are due (nothing popped)");
+    }
+    if (out_off) HIP_CHECK(hipMemcpyAsync(out_off, offs, ((size_t)H + 1) * 8, hipMemcpyDeviceToDevice, st));
+    if (total == 0) {
+        HIP_CHECK(hipStreamSynchronize(st));
+        return;
+    }
+    EvqState* ds = (EvqState*)q.state.get(sizeof(EvqState));
+    const EvqState init{~0ull, 0u, 0u};
+    HIP_CHECK(hipMemcpyAsync(ds, &init, sizeof(EvqState), hipMemcpyHostToDevice, st));
+    k_evq_pop_copy<<<grid_for(total, 2048), kThreads, 0, st>>>(A.ptrs(), head, offs, H, total, out_time, out_src, out_id,
+                                                               out_tag);
+    k_evq_pop_commit<<<grid_for(H, 2048), kThreads, 0, st>>>(A.ptrs(), host_off, head, (uint64_t*)q.last_popped.p,
+                                                             new_head, H, ds);
+    HIP_CHECK(hipGetLastError());
+    const EvqState s = evq_read_state(ds, st);
+    q.live -= total;
+    q.min_next = s.min_head;
+    evq_fill_result(q, total, res);
+}
+
 __global__ void k_widen_edges(size_t n, const uint16_t* __restrict__ s16, const uint16_t* __restrict__ d16,
                               const uint32_t* __restrict__ l32, uint32_t* __restrict__ src, uint32_t* __restrict__ dst,
                               uint64_t* __restrict__ lat) {
@@ -3923,6 +4073,97 @@ int srg_send_packets_device(srg_ctx* ctx, const srg_send_batch* sb, const srg_pa
         HIP_CHECK(hipStreamSynchronize(st));
         if (res) res->ev.ms_total = ms_since(t0);
     });
+}
+
+int srg_event_queues_create(srg_ctx* ctx, uint32_t num_hosts, uint64_t reserve_events, srg_event_queues** out,
+                            char* errbuf, size_t errlen) {
+    if (!ctx || !out) {
+        set_err(errbuf, errlen, "null argument");
+        return SRG_ERR_ARG;
+    }
+    *out = nullptr;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    return guard(errbuf, errlen, [&]() {
+        HIP_CHECK(hipSetDevice(ctx->device));
+        std::unique_ptr<srg_event_queues> q(new srg_event_queues);
+        q->ctx = ctx;
+        q->num_hosts = num_hosts;
+        const size_t hb = ((size_t)num_hosts + 1) * 8;
+        for (auto& s : q->set) {
+            HIP_CHECK(hipMemsetAsync(s.host_off.get(hb), 0, hb, ctx->stream));
+            HIP_CHECK(hipMemsetAsync(s.head.get(hb), 0, hb, ctx->stream));
+            s.reserve(reserve_events);
+        }
+        HIP_CHECK(hipMemsetAsync(q->last_popped.get(hb), 0, hb, ctx->stream));
+        for (DevBuf* b : {&q->dead, &q->dead_excl, &q->new_head, &q->cnt, &q->offs}) b->get(hb);
+        q->state.get(sizeof(EvqState));
+        HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        *out = q.release();
+    });
+}
+
+void srg_event_queues_destroy(srg_event_queues* q) {
+    if (!q) return;
+    {
+        std::lock_guard<std::mutex> lk(q->ctx->mu);
+        (void)hipSetDevice(q->ctx->device);
+    }
+    delete q;
+}
+
+uint32_t srg_event_queues_merge_tile(void) { return (uint32_t)EVQ_TILE; }
+
+int srg_event_queues_push_device(srg_event_queues* q, const srg_event_batch* b, const uint64_t* deliver,
+                                 const uint32_t* order, uint64_t num_order, const uint64_t* tag, void* hip_stream,
+                                 srg_queue_result* res, char* errbuf, size_t errlen) {
+    if (!q || !b ||
+        (num_order && (!deliver || !order || !b->src_host || !b->dst_host || !b->src_event_id))) {
+        set_err(errbuf, errlen, "null argument");
+        return SRG_ERR_ARG;
+    }
+    srg_ctx* ctx = q->ctx;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    return guard(errbuf, errlen, [&]() {
+        auto t0 = std::chrono::steady_clock::now();
+        HIP_CHECK(hipSetDevice(ctx->device));
+        hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+        if (res) res->ms_total = 0;
+        evq_push(*q, b, deliver, order, num_order, tag, st, res);
+        HIP_CHECK(hipStreamSynchronize(st));
+        if (res) res->ms_total = ms_since(t0);
+    });
+}
+
+int srg_event_queues_pop_device(srg_event_queues* q, uint64_t until_ns, uint64_t out_capacity, uint64_t* out_time,
+                                uint32_t* out_src, uint64_t* out_id, uint64_t* out_tag, uint64_t* out_off,
+                                void* hip_stream, srg_queue_result* res, char* errbuf, size_t errlen) {
+    if (!q || (out_capacity && (!out_time || !out_tag || !out_off))) {
+        set_err(errbuf, errlen, "null argument");
+        return SRG_ERR_ARG;
+    }
+    srg_ctx* ctx = q->ctx;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    return guard(errbuf, errlen, [&]() {
+        auto t0 = std::chrono::steady_clock::now();
+        HIP_CHECK(hipSetDevice(ctx->device));
+        hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+        if (res) res->ms_total = 0;
+        evq_pop(*q, until_ns, out_capacity, out_time, out_src, out_id, out_tag, out_off, st, res);
+        HIP_CHECK(hipStreamSynchronize(st));
+        if (res) res->ms_total = ms_since(t0);
+    });
+}
+
+int srg_next_window(uint64_t min_next_event_ns, uint64_t runahead_ns, uint64_t end_time_ns, uint64_t* window_start_ns,
+                    uint64_t* window_end_ns) {
+    if (!runahead_ns || !window_start_ns || !window_end_ns) return -SRG_ERR_ARG;  // assert_ne!(runahead, ZERO)
+    const uint64_t start = min_next_event_ns;
+    uint64_t end = start > UINT64_MAX - runahead_ns ? UINT64_MAX : start + runahead_ns;  // checked_add, else MAX
+    end = end < end_time_ns ? end : end_time_ns;
+    if (!(start < end)) return 0;
+    *window_start_ns = start;
+    *window_end_ns = end;
+    return 1;
 }
 
 const char* srg_version(void) { return "shadow_amd routing 0.3 (gfx950, dense FW u32/u64 + tight-DAG loss, RCCL row-block FW, sparse BF, event batches)"; }

@@ -15,6 +15,11 @@ send_packets / send_packets_device (srg_send_packets_device) start higher up, at
 (worker.rs:374-390: chance >= 1.0f32 - packet_loss, payload > 0, not bootstrapping), take the
 table in either form a RoutingInfo keeps (DevicePathTable), and count the sent packets per node
 pair (increment_packet_count, worker.rs:395).  Only the RNG draw stays with the caller: `chance`.
+
+EventQueues (srg_event_queues_*) keeps the per-host packet-event queues themselves in HBM across
+rounds: push merges a round's ordered batch into the backlog, pop takes a window's events out in
+the reference's order (event_queue.rs:10-55, host.rs:809-818), next_window is the controller's step
+(controller.rs:88-112).
 """
 import ctypes
 
@@ -220,3 +225,131 @@ def synthetic_round(n, num_hosts, table_n, seed=7, t0=10**12, runahead=5_000_000
     batch["payload_size"] = np.where(rng2.random(n) < zero_payload, 0, rng2.integers(1, 1461, n)).astype(np.uint32)
     table = (rng2.random((table_n, table_n), dtype=np.float32) * np.float32(2.0 * loss)).astype(np.float32)
     return batch, t0 + runahead, table
+
+
+class TimeBackwardError(NetGraphError):
+    """A pushed event earlier than its host's last popped event: EventQueue::push's assert!
+    (event_queue.rs:33)."""
+
+
+def _raise_queue(rc, msg):
+    if rc == N.SRG_ERR_EVENT_ORDER:
+        raise EventOrderError(rc, msg)
+    if rc == N.SRG_ERR_TIME_BACKWARD:
+        raise TimeBackwardError(rc, msg)
+    _raise(rc, msg)
+
+
+def next_window(min_next_event_ns, runahead_ns, end_time_ns):
+    """The controller's window step (controller.rs:88-112, srg_next_window): (start, end), or None
+    when the simulation is over.  runahead 0 is the reference's assert_ne!: NetGraphError."""
+    ws, we = ctypes.c_uint64(), ctypes.c_uint64()
+    rc = N.lib().srg_next_window(int(min_next_event_ns), int(runahead_ns), int(end_time_ns), ctypes.byref(ws),
+                                 ctypes.byref(we))
+    if rc < 0:
+        _raise(-rc, "srg_next_window: runahead must not be zero")
+    return (int(ws.value), int(we.value)) if rc else None
+
+
+class EventQueues:
+    """The per-host packet-event queues, resident in HBM across rounds (srg_event_queues_*,
+    event_queue.hip.h).  The round loop: pop(window_end) -> the hosts run -> send() at the barrier
+    -> next_window(queues.min_next_event_ns, runahead, end_time).  Local events stay with the host."""
+
+    def __init__(self, router, num_hosts, reserve=0):
+        self.router, self.num_hosts = router, int(num_hosts)
+        self.dev = torch.device(f"cuda:{router.device}")
+        h = ctypes.c_void_p()
+        err = ctypes.create_string_buffer(1024)
+        rc = N.lib().srg_event_queues_create(router._h, self.num_hosts, int(reserve), ctypes.byref(h), err, len(err))
+        if rc != N.SRG_OK:
+            _raise(rc, err.value.decode(errors="replace"))
+        self._h = h
+        self.num_queued = 0
+        self.min_next_event_ns = 2**64 - 1
+
+    def close(self):
+        if self._h:
+            N.lib().srg_event_queues_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __len__(self):
+        return self.num_queued
+
+    def _done(self, rc, res, err):
+        if rc != N.SRG_OK:
+            _raise_queue(rc, err.value.decode(errors="replace"))
+        self.num_queued, self.min_next_event_ns = int(res.num_queued), int(res.min_next_event_ns)
+        return res.as_dict()
+
+    def push(self, dbatch, deliver_t, order_t, num_order, tags_t=None, stream=None):
+        """dbatch: the DeviceEventBatch / DeviceSendBatch that order_packet_events_device /
+        send_packets_device took; deliver_t, order_t: what it wrote; num_order: n / num_sent;
+        tags_t: int64 [n] on the device (None: an event's tag is its index)."""
+        res = N.QueueResult()
+        err = ctypes.create_string_buffer(1024)
+        b = dbatch.as_struct()
+        s = stream if stream is not None else torch.cuda.current_stream(self.dev)
+        rc = N.lib().srg_event_queues_push_device(
+            self._h, ctypes.byref(b), deliver_t.data_ptr(), order_t.data_ptr(), int(num_order),
+            tags_t.data_ptr() if tags_t is not None else None, ctypes.c_void_p(s.cuda_stream), ctypes.byref(res), err,
+            len(err))
+        return self._done(rc, res, err)
+
+    def pop_device(self, until_ns, capacity, out_time_t, out_src_t, out_id_t, out_tag_t, out_off_t, stream=None):
+        """Raw call; returns (rc, result dict, message) and raises nothing: a short capacity is
+        SRG_ERR_ARG with num_moved = the count needed."""
+        res = N.QueueResult()
+        err = ctypes.create_string_buffer(1024)
+        s = stream if stream is not None else torch.cuda.current_stream(self.dev)
+
+        def ptr(t):
+            return t.data_ptr() if t is not None else None
+        rc = N.lib().srg_event_queues_pop_device(
+            self._h, int(until_ns), int(capacity), ptr(out_time_t), ptr(out_src_t), ptr(out_id_t), ptr(out_tag_t),
+            ptr(out_off_t), ctypes.c_void_p(s.cuda_stream), ctypes.byref(res), err, len(err))
+        if rc == N.SRG_OK:
+            self.num_queued, self.min_next_event_ns = int(res.num_queued), int(res.min_next_event_ns)
+        return rc, res.as_dict(), err.value.decode(errors="replace")
+
+    def pop(self, until_ns):
+        """Pops every event with time < until_ns.  Returns host arrays (time u64, src_host u32,
+        src_event_id u64, tag u64, host_offsets u64 [H + 1], result): grouped by host, each host's
+        slice in pop order.  Sized with a capacity-0 call first."""
+        dev = self.dev
+        off = torch.empty(self.num_hosts + 1, dtype=torch.int64, device=dev)
+        rc, res, msg = self.pop_device(until_ns, 0, None, None, None, None, off)
+        n = 0
+        if rc == N.SRG_ERR_ARG and res["num_moved"] > 0:
+            n = int(res["num_moved"])
+            t = torch.empty(n, dtype=torch.int64, device=dev)
+            src = torch.empty(n, dtype=torch.int32, device=dev)
+            eid = torch.empty(n, dtype=torch.int64, device=dev)
+            tag = torch.empty(n, dtype=torch.int64, device=dev)
+            rc, res, msg = self.pop_device(until_ns, n, t, src, eid, tag, off)
+        if rc != N.SRG_OK:
+            _raise_queue(rc, msg)
+        if n == 0:
+            z = np.zeros(0, np.uint64)
+            return z, np.zeros(0, np.uint32), z.copy(), z.copy(), off.cpu().numpy().view(np.uint64), res
+        return (t.cpu().numpy().view(np.uint64), src.cpu().numpy().view(np.uint32), eid.cpu().numpy().view(np.uint64),
+                tag.cpu().numpy().view(np.uint64), off.cpu().numpy().view(np.uint64), res)
+
+    def send(self, dbatch, table, counts=None, tags=None):
+        """send_packets_device, then push: the round's sent events enter the queues, the dropped
+        ones never do.  tags: int64 [n] tensor on the device, or None.  Returns (send result,
+        queue result, status uint8 tensor)."""
+        dev, n = self.dev, dbatch.n
+        status = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)[:n]
+        deliver = torch.empty(max(n, 1), dtype=torch.int64, device=dev)[:n]
+        order = torch.empty(max(n, 1), dtype=torch.int32, device=dev)[:n]
+        off = torch.empty(dbatch.num_hosts + 1, dtype=torch.int64, device=dev)
+        sres = send_packets_device(self.router, dbatch, table, status, deliver, order, off, counts)
+        qres = self.push(dbatch, deliver, order, sres["num_sent"], tags)
+        return sres, qres, status
