@@ -79,7 +79,8 @@ typedef struct srg_stats {
     double ms_d2h;              /* device -> host copies (host entry points only) */
     int32_t path_kind;          /* SRG_PATH_* below */
     int32_t loss_rounds;        /* max fold rounds over rows (DAG depth + 1) */
-    uint64_t multi_pred_pairs;  /* (s,t) pairs with >1 tight predecessor (slow path) */
+    uint64_t multi_pred_pairs;  /* (s,t) pairs with >1 tight predecessor (slow path); u64 keys: the pairs whose
+                                 * keys' low words tie, which the loss pass decides exactly (an upper bound) */
     uint64_t relaxations;       /* min-plus relaxations issued by the FW kernels */
     uint64_t essential_edges;   /* edges with W[u][t] == D[u][t] (candidates for tightness) */
     int32_t scan_kind;          /* SRG_SCAN_* below */
@@ -240,6 +241,18 @@ void srg_destroy(srg_ctx* ctx);
 #define SRG_OPT_SCAN_MIRROR_CAP 42   /* pairs the mirror's exact-key worklist holds per launch; 0 (default) =
                                      * 1 / 1024 of the launch's pairs (at least 256); at most what the packed
                                      * predecessor rows leave free (half the launch's pairs) */
+#define SRG_OPT_LOSS_KIND 43         /* read-only: the last dense build's loss pass: 0 = none (no dense build, or
+                                     * no local source), 1 = per-row fold in LDS (k_loss_rows), 2 = global-memory
+                                     * fold over the essential entries (k_loss_round_sparse: rows too long for
+                                     * LDS), 3 = dense-scan fold (k_loss_round).  The tests read it to prove which
+                                     * pass they ran; the limits that select it (the list's LM_T x LM_E, the
+                                     * mirror's step limit, the largest V of the LDS fold) come from
+                                     * srg_internal_loss_limits (csrc/internal.h), and the environment switch
+                                     * SRG_LOSS_ROWS_MAX_V (csrc/env_switches.h) lowers the last one */
+#define SRG_LOSS_NONE 0
+#define SRG_LOSS_ROWS_LDS 1
+#define SRG_LOSS_GLOBAL_ENTRIES 2
+#define SRG_LOSS_DENSE_SCAN 3
 int srg_set_option(srg_ctx* ctx, int option, double value);
 /* current value of an option (SRG_OK), or SRG_ERR_ARG for an unknown option */
 int srg_get_option(srg_ctx* ctx, int option, double* value);

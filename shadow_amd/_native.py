@@ -58,6 +58,11 @@ SRG_OPT_FW_XCD_ORDER = 39
 SRG_OPT_SCAN_MIRROR = 40
 SRG_OPT_SCAN_MIRRORED = 41
 SRG_OPT_SCAN_MIRROR_CAP = 42
+SRG_OPT_LOSS_KIND = 43
+SRG_LOSS_NONE = 0
+SRG_LOSS_ROWS_LDS = 1
+SRG_LOSS_GLOBAL_ENTRIES = 2
+SRG_LOSS_DENSE_SCAN = 3
 SRG_ALGO_AUTO = 0
 SRG_ALGO_DENSE = 1
 SRG_ALGO_SPARSE = 2
@@ -356,5 +361,14 @@ def lib():
     L.srg_get_option.argtypes = [c.c_void_p, c.c_int, c.POINTER(c.c_double)]
     L.srg_comm_size.restype = c.c_int
     L.srg_comm_size.argtypes = [c.c_void_p, c.POINTER(c.c_int), c.POINTER(c.c_int)]
+    L.srg_internal_loss_limits.restype = None
+    L.srg_internal_loss_limits.argtypes = [_u32p]
     _lib = L
     return L
+
+
+def loss_limits():
+    """srg_internal_loss_limits: (LM_T, LM_E, MIRROR_STEPS, largest V of the per-row LDS loss fold)."""
+    out = (ctypes.c_uint32 * 4)()
+    lib().srg_internal_loss_limits(out)
+    return tuple(int(x) for x in out)

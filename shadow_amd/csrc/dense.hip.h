@@ -373,21 +373,23 @@ bool run_dense(srg_ctx& c, const DevGraph& g, const Plan& pl, const uint32_t* no
         }
         HIP_CHECK(hipGetLastError());
         const size_t lds_rows = loss_rows_lds(V);
+        // the per-row LDS fold when a row fits (SRG_LOSS_ROWS_MAX_V, tests: only below that V)
+        const bool rows_lds = V <= srg_env::loss_rows_max_v(LOSS_ROWS_MAX_V);
         // Triangular scan (SRG_OPT_SCAN_MIRROR): on an undirected graph whose rows are
         // the vertices in order, one rank, u32 keys, per-row LDS loss, tight_v5 scans only the pairs
         // (source block c, target tile b >= c) and k_pred_mirror derives the packed entries below
         // the diagonal.  Every other build scans every pair.
         bool mirror = c.scan_mirror && !g.directed && pl.G == 1 && !multi && !simulated && nloc == n && P.ident &&
-                      !v5lo && lds_rows <= 150 * 1024;
+                      !v5lo && rows_lds;
         // host entry, one rank, per-row LDS loss: scan groups interleaved with the loss rows (mirrored:
         // one group more, the later groups scan little and their rows keep the link fed: C3 host entry
         // 3 / 4 / 5 groups 44.3 / 43.0 / 42.7 ms, profiles/r07/scan_mirror)
         const uint32_t scan_groups = c.scan_groups ? (uint32_t)c.scan_groups : mirror ? 4u : 3u;
-        const bool interleave = sink_rows && lds_rows <= 150 * 1024 && scan_groups > 1;
+        const bool interleave = sink_rows && rows_lds && scan_groups > 1;
         if (interleave) set_lds(k_loss_rows<K, true>, lds_rows);
         // the per-row LDS loss pass reads PRED packed with each single predecessor's {u, 1 - loss}
         // (k_pred_pack, after each scan group); the global-memory fold the entry indices
-        uint32_t* PREDK = lds_rows <= 150 * 1024 ? (uint32_t*)c.b_PRED2.get(nmax * Vp * 8) : nullptr;
+        uint32_t* PREDK = rows_lds ? (uint32_t*)c.b_PRED2.get(nmax * Vp * 8) : nullptr;
         auto pack_pred = [&](uint32_t r0, uint32_t r1) {
             const uint32_t nsb = (r1 - r0 + 127) / 128, nt8 = (nbTT5 + 7) / 8;
             k_pred_pack<<<8u * nt8 * nsb, 256, 0, st>>>(PRED, Vp, r0, r1, NT, nbTT5, nsb, ent_ub, (uint2*)PREDK,
@@ -478,7 +480,8 @@ bool run_dense(srg_ctx& c, const DevGraph& g, const Plan& pl, const uint32_t* no
                 HIP_CHECK(hipStreamSynchronize(st));
                 rounds = (int)rb_get<uint32_t>(c, MS_CHANGED);
                 loss_written = true;
-            } else if (lds_rows <= 150 * 1024) {
+                c.loss_kind = SRG_LOSS_ROWS_LDS;
+            } else if (rows_lds) {
                 // per-row Gauss-Seidel in LDS, writes out_loss directly
                 set_lds(k_loss_rows<K, true>, lds_rows);
                 HIP_CHECK(hipMemsetAsync(&P.flags->changed, 0, 4, st));
@@ -503,7 +506,9 @@ bool run_dense(srg_ctx& c, const DevGraph& g, const Plan& pl, const uint32_t* no
                 HIP_CHECK(hipStreamSynchronize(st));
                 rounds = (int)rb_get<uint32_t>(c, MS_CHANGED);
                 loss_written = true;
+                c.loss_kind = SRG_LOSS_ROWS_LDS;
             } else {
+                c.loss_kind = SRG_LOSS_GLOBAL_ENTRIES;
                 float* L0 = (float*)c.b_L0.get(nmax * Vp * 4);
                 float* L1 = (float*)c.b_L1.get(nmax * Vp * 4);
                 k_fill<float><<<grid_for((size_t)nloc * Vp), kThreads, 0, st>>>(L0, (size_t)nloc * Vp, 1.0f);
@@ -544,6 +549,7 @@ bool run_dense(srg_ctx& c, const DevGraph& g, const Plan& pl, const uint32_t* no
     } else {
         scan_kind = SRG_SCAN_DENSE;
         if (nloc) {
+            c.loss_kind = SRG_LOSS_DENSE_SCAN;
             const size_t lds3 = (size_t)2 * KC * (TS + VE) * sizeof(K);
             set_lds(tight_scan<K, TS, KC>, lds3);
             tight_scan<K, TS, KC><<<dim3((unsigned)(Vp / TS), (nloc + TS - 1) / TS), 256, lds3, st>>>(D, W, Vp, lnodes,

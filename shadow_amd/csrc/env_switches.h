@@ -65,6 +65,18 @@ static inline bool codec_slow_after(size_t& chunk) {
 static inline bool prefault_on() { return !equals("SRG_PREFAULT", "0"); }
 // [A/B] SRG_NO_KEY_D2H (set): latency rows leave as u64 ns, not as u32 keys widened on the host
 static inline bool no_key_d2h() { return is_set("SRG_NO_KEY_D2H"); }
+// [test] SRG_LOSS_ROWS_MAX_V=n: the dense build's per-row LDS loss fold only for V <= n, so a small
+// graph takes the global-memory fold (and, as at large V, neither the mirrored scan, the interleaved
+// scan groups nor the packed predecessor rows).  Only ever lowers the limit: `limit` is the largest V
+// whose rows fit LDS, and a value above it (or no value) returns it unchanged.
+static inline unsigned loss_rows_max_v(unsigned limit) {
+    const char* e = std::getenv("SRG_LOSS_ROWS_MAX_V");
+    if (!e || !*e) return limit;
+    char* end = nullptr;
+    const unsigned long long v = std::strtoull(e, &end, 10);
+    if (end == e || *end) return limit;  // not a number: ignored
+    return v < limit ? (unsigned)v : limit;
+}
 // [A/B] SRG_CREATE_WARM=0...: srg_create skips its warm-up
 static inline bool create_warm_off() { return first_char_is("SRG_CREATE_WARM", '0'); }
 

@@ -30,6 +30,9 @@ int srg_internal_compute_table(srg_ctx* ctx, const srg_edge_list* graph, const u
 srg_table* srg_internal_table_get(srg_ctx* ctx, size_t bytes, void** host);
 // plan.h's scan_group_cut_tri as run_dense calls it (the tests read the mirrored build's groups)
 uint32_t srg_internal_scan_group_cut_tri(uint32_t q, uint32_t ng, uint32_t nblocks);
+// the loss pass's and the mirror's limits (tight_sparse.hip.h), for the tests that must straddle them:
+// out = {LM_T, LM_E, MIRROR_STEPS, the largest V whose row the per-row LDS fold takes}
+void srg_internal_loss_limits(uint32_t out[4]);
 // back to its pool (still page-locked), or freed when the pool is closed or full
 void srg_internal_table_put(srg_table* t);
 }

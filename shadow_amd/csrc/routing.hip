@@ -842,6 +842,7 @@ struct srg_ctx {
     int fw_xcd_order = 1;               // symmetric FW bulk: tiles dealt to the XCDs in Z-order runs (SRG_OPT_FW_XCD_ORDER)
     int scan_mirror = 1;                // undirected one-rank builds: scan the pairs (tile >= source block), mirror the rest (SRG_OPT_SCAN_MIRROR)
     int scan_mirrored = 0;              // the last build: 0 = every pair scanned, 1 = mirrored, 2 = mirrored, then rescanned (SRG_OPT_SCAN_MIRRORED)
+    int loss_kind = 0;                  // the last dense build's loss pass, SRG_LOSS_* (SRG_OPT_LOSS_KIND)
     int scan_mirror_cap = 0;            // the mirror worklist's capacity in pairs per launch (0 = 1 / 1024 of the rows' pairs) (SRG_OPT_SCAN_MIRROR_CAP)
     DevBuf b_tri;                       // the triangular scan launches' block lists
     int test_fault = 0;                 // TEST HOOK (SRG_OPT_TEST_FAULT): 1 = zero D after FW, 2 = stale FW sync words
@@ -2160,6 +2161,7 @@ void compute_device(srg_ctx& c, const DevGraph& g, const uint32_t* nodes, uint32
     HIP_CHECK(hipStreamSynchronize(c.aux_stream));  // nothing of an aborted call still writes WL / PRED
     HIP_CHECK(hipStreamSynchronize(c.comm_stream));  // ... or the essential-entry counts
     c.scan_mirrored = 0;
+    c.loss_kind = SRG_LOSS_NONE;
     if (g.V == 0) {
         if (n) fail(SRG_ERR_ARG, "nodes given for an empty graph");
         return;
@@ -3625,6 +3627,7 @@ int srg_get_option(srg_ctx* ctx, int option, double* value) {
         case SRG_OPT_SCAN_MIRROR: *value = ctx->scan_mirror; break;
         case SRG_OPT_SCAN_MIRRORED: *value = ctx->scan_mirrored; break;
         case SRG_OPT_SCAN_MIRROR_CAP: *value = ctx->scan_mirror_cap; break;
+        case SRG_OPT_LOSS_KIND: *value = ctx->loss_kind; break;
         default: return SRG_ERR_ARG;
     }
     return SRG_OK;
@@ -3655,6 +3658,13 @@ int srg_internal_compute_table(srg_ctx* ctx, const srg_edge_list* graph, const u
 
 uint32_t srg_internal_scan_group_cut_tri(uint32_t q, uint32_t ng, uint32_t nblocks) {
     return scan_group_cut_tri(q, ng, nblocks);
+}
+
+void srg_internal_loss_limits(uint32_t out[4]) {
+    out[0] = LM_T;
+    out[1] = LM_E;
+    out[2] = MIRROR_STEPS;
+    out[3] = LOSS_ROWS_MAX_V;
 }
 
 srg_table* srg_internal_table_get(srg_ctx* ctx, size_t bytes, void** host) {

@@ -619,6 +619,12 @@ constexpr uint32_t U_SELF = 0xFFFFFFFFu, U_NONE = 0xFFFFFFFEu, U_MULTI = 0xFFFFF
 constexpr uint32_t U_MLIST = 0xF0000000u;  // U_MLIST + i: multi target i of the LDS list
 constexpr uint32_t LM_T = 32, LM_E = 16;
 constexpr size_t loss_rows_lds(uint32_t V) { return (size_t)V * 12 + LM_T * (4 + 4 + LM_E * 8) + 16; }
+// the largest V whose row fits the fold's LDS budget (150 KiB of the CU's 160); longer rows take the
+// global-memory fold (k_loss_round_sparse)
+constexpr size_t LOSS_ROWS_LDS_BYTES = 150 * 1024;
+constexpr uint32_t LOSS_ROWS_MAX_V = (uint32_t)((LOSS_ROWS_LDS_BYTES - loss_rows_lds(0)) / 12);
+static_assert(loss_rows_lds(LOSS_ROWS_MAX_V) <= LOSS_ROWS_LDS_BYTES && loss_rows_lds(LOSS_ROWS_MAX_V + 1) > LOSS_ROWS_LDS_BYTES,
+              "LOSS_ROWS_MAX_V");
 
 // PK: PRED rows as tight_v5<true> writes them ({u, 1 - loss} or {marker, 0}, ldp uint2 per row)
 template <class K, bool PK>
