@@ -550,6 +550,68 @@ int srg_event_queues_pop_device(srg_event_queues* q, uint64_t until_ns, uint64_t
 int srg_next_window(uint64_t min_next_event_ns, uint64_t runahead_ns, uint64_t end_time_ns,
                     uint64_t* window_start_ns, uint64_t* window_end_ns);
 
+/* ---- the routes a table's paths take; per-edge packet loads --------------------------------
+ * The reference keeps no routes: petgraph's dijkstra returns scores only (mod.rs:190-208).  They
+ * can be read back from a finished shortest-path table alone, because a Dijkstra label is
+ * label(u) + edge (PathProperties::add, mod.rs:321-331: the latency adds, the loss is the f32 left
+ * fold 1 - (1 - L)(1 - p)): for every s != t the table holds a vertex u and an in-edge e = (u, t)
+ * with D[s][u] + lat(e) == D[s][t] and bits(fold(L[s][u], loss(e))) == bits(L[s][t]), the source's
+ * own label being (0, +0.0f), not the diagonal (which holds the raw self-loop weight).  Walking
+ * that relation back from t gives a route; no buffer of the build is used, so a table of either
+ * build, in either form of srg_path_table_dev, from one rank or many, is traced the same way.
+ *   Tie rule (makes the route unique): in-edges of a vertex are the edges (u, cur), u != cur; on an
+ *   undirected graph an edge stored as (cur, u) counts too; self-loops are never candidates; among
+ *   the in-edges that satisfy both equalities the one with the SMALLEST EDGE INDEX (position in
+ *   srg_edge_list) is the route's edge.
+ *   The route is *a* minimal path reproducing the table's (latency, loss) bits, made unique by the
+ *   tie rule; the reference's own choice among bit-equal predecessors is unobservable.
+ *   Diagonal: the route s -> s is one hop, the self-loop edge of s (mod.rs:210-217; the smallest
+ *   index if the list holds several); none: SRG_ERR_NO_EDGE with the reference's text.
+ *   Table shape: the table must cover every vertex in NodeIndex order (table->n == num_vertices,
+ *   position = vertex) and table->packet_loss is required; anything else is SRG_ERR_ARG.
+ *   Rectangular or subset tables are out of scope.
+ *   A query index >= n is SRG_ERR_ARG; so is an edge of latency 0 between two vertices in
+ *   graph_dev (the walk ends because latencies are >= 1; a hop cap of num_vertices backs that up).
+ *   A get_direct_paths table is not a fold from (0, 0) and is refused with SRG_ERR_ROUTE: its
+ *   routes are the single edges.
+ *   The in-edge lists are rebuilt from graph_dev on every call (nothing is cached between calls:
+ *   the edge arrays may be rewritten in place); the workspace is the context's.
+ *   Both calls return after their stream work is complete, and leave the hop arrays, the offsets
+ *   and edge_packets_dev untouched on any error: every pair is walked first, then committed.   */
+#define SRG_ERR_ROUTE 13   /* a pair whose table entry no in-edge explains: the table is not a
+                              shortest-path table of this graph (wrong graph, a direct-path table,
+                              a damaged entry) */
+typedef struct srg_route_result {
+    uint64_t num_pairs;    /* pairs walked (loads: the nonzero count entries) */
+    uint64_t total_hops;   /* sum of route lengths (trace: also the capacity needed) */
+    uint64_t bad_pair;     /* SRG_ERR_ROUTE: index of the first unexplained query (loads: s*n+t);
+                              else UINT64_MAX */
+    uint32_t max_hops, reserved;
+    double ms_total;
+} srg_route_result;
+
+/* Device pointers throughout.  Query i is the path src_dev[i] -> dst_dev[i] (NodeIndex values).
+ * Its route is out_hop_edge_dev[out_hop_offsets_dev[i] .. out_hop_offsets_dev[i + 1]), edge indices
+ * in order from s to t; out_hop_vertex_dev (same slots) is the vertex each hop arrives at, so the
+ * last one is t.  Sizing as srg_event_queues_pop_device: with hop_capacity 0 every output may be
+ * NULL; more hops needed than hop_capacity: SRG_ERR_ARG, total_hops = the need, nothing written.
+ * SRG_ERR_ROUTE names the pair (the source's and the target's NodeIndex) in errbuf.
+ * num_pairs < 2^31 - 1.                                                                        */
+int srg_trace_routes_device(srg_ctx* ctx, const srg_edge_list* graph_dev, const srg_path_table_dev* table,
+                            const uint32_t* src_dev, const uint32_t* dst_dev, uint64_t num_pairs,
+                            uint64_t hop_capacity, uint64_t* out_hop_offsets_dev /* [num_pairs+1] */,
+                            uint32_t* out_hop_edge_dev /* [hop_capacity] edge indices, s -> t */,
+                            uint32_t* out_hop_vertex_dev /* may be NULL: the vertex each hop arrives at */,
+                            void* hip_stream, srg_route_result* result, char* errbuf, size_t errlen);
+
+/* Per-edge packet loads: every nonzero entry [s, t] of a packet-count table (what
+ * srg_send_packets_device accumulates) is added to every edge of the route s -> t; a diagonal
+ * count goes to the self-loop edge.  Saturating at UINT64_MAX.  n * n < 2^31 - 1.              */
+int srg_link_loads_device(srg_ctx* ctx, const srg_edge_list* graph_dev, const srg_path_table_dev* table,
+                          const uint64_t* packet_counts_dev /* [n*n] by position */,
+                          uint64_t* edge_packets_dev /* [num_edges], NOT cleared: accumulated, saturating */,
+                          void* hip_stream, srg_route_result* result, char* errbuf, size_t errlen);
+
 /* Library build/version string. */
 const char* srg_version(void);
 

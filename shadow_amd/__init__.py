@@ -6,6 +6,7 @@ include/shadow_routing.h.  See DESIGN.md.
 """
 from .graph import (Edges, HipError, LocalGroup, MultiRouter, NetGraphError, NetworkGraph, PathProperties, PathTable,
                     Router, RoutingInfo, RoutingPanic, generate_routing_info)
+from ._native import RouteResult  # result of shadow_amd.routes (trace_routes, link_loads)
 
 __all__ = ["Edges", "HipError", "LocalGroup", "MultiRouter", "NetGraphError", "NetworkGraph", "PathProperties", "PathTable", "Router",
-           "RoutingInfo", "RoutingPanic", "generate_routing_info"]
+           "RoutingInfo", "RoutingPanic", "RouteResult", "generate_routing_info"]

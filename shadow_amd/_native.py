@@ -23,6 +23,7 @@ SRG_ERR_RCCL = 9
 SRG_ERR_INTERNAL = 10
 SRG_ERR_EVENT_ORDER = 11
 SRG_ERR_TIME_BACKWARD = 12
+SRG_ERR_ROUTE = 13
 
 SRG_PATH_DENSE_U32 = 0
 SRG_PATH_DENSE_U64 = 1
@@ -164,6 +165,20 @@ class QueueResult(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class RouteResult(ctypes.Structure):
+    _fields_ = [
+        ("num_pairs", ctypes.c_uint64),
+        ("total_hops", ctypes.c_uint64),
+        ("bad_pair", ctypes.c_uint64),
+        ("max_hops", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32),
+        ("ms_total", ctypes.c_double),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class Stats(ctypes.Structure):
     _fields_ = [
         ("ms_total", ctypes.c_double),
@@ -219,6 +234,7 @@ EXPORTS = [
     "srg_send_packets_device", "srg_routing_info_key_tables", "srg_routing_info_add_packet_counts",
     "srg_event_queues_create", "srg_event_queues_destroy", "srg_event_queues_merge_tile",
     "srg_event_queues_push_device", "srg_event_queues_pop_device", "srg_next_window",
+    "srg_trace_routes_device", "srg_link_loads_device",
 ]
 
 _lib = None
@@ -324,6 +340,14 @@ def lib():
         c.POINTER(QueueResult), c.c_char_p, c.c_size_t]
     L.srg_next_window.restype = c.c_int
     L.srg_next_window.argtypes = [c.c_uint64, c.c_uint64, c.c_uint64, _u64p, _u64p]
+    L.srg_trace_routes_device.restype = c.c_int
+    L.srg_trace_routes_device.argtypes = [
+        c.c_void_p, c.POINTER(EdgeList), c.POINTER(PathTableDev), c.c_void_p, c.c_void_p, c.c_uint64, c.c_uint64,
+        c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.POINTER(RouteResult), c.c_char_p, c.c_size_t]
+    L.srg_link_loads_device.restype = c.c_int
+    L.srg_link_loads_device.argtypes = [
+        c.c_void_p, c.POINTER(EdgeList), c.POINTER(PathTableDev), c.c_void_p, c.c_void_p, c.c_void_p,
+        c.POINTER(RouteResult), c.c_char_p, c.c_size_t]
     L.srg_routing_info_build.restype = c.c_int
     L.srg_routing_info_build.argtypes = [c.c_void_p, c.POINTER(EdgeList), c.c_void_p, c.c_uint32, c.c_int,
                                          c.POINTER(c.c_void_p), c.POINTER(Stats), c.c_char_p, c.c_size_t]

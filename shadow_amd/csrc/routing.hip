@@ -11,7 +11,8 @@
 // Files: env_switches.h (every SRG_* environment switch), host_pool.h (host worker pool), plan.h
 // (rank / XCD / scan-group splits) -- all three without HIP; dense.hip.h (run_dense) and
 // sparse_run.hip.h (run_sparse, choose_sparse), sections of this translation unit; the device
-// headers (kernels, tight_sparse, sparse, sparse_ds, events, xchg).  Still here, in order: the
+// headers (kernels, tight_sparse, sparse, sparse_ds, events, xchg); routes.hip.h (route tracing and
+// link loads over a finished table, rule in route_rule.h), a section too.  Still here, in order: the
 // validation / W / certify / extract kernels, the context (srg_ctx), prelude(), HostSink, the FW
 // schedules (stream_hop, fw_blocked, SymFw, FwOverlap), compute_device, direct paths, packet
 // events, the H2D codec, host_entry, extern "C".
@@ -53,6 +54,7 @@
 #include "sparse.hip.h"
 #include "sparse_ds.hip.h"
 #include "events.hip.h"
+#include "route_rule.h"
 #include "event_queue.hip.h"
 #include "xchg.hip.h"
 
@@ -850,6 +852,9 @@ struct srg_ctx {
     double ms_create_runtime = 0, ms_create_lib = 0;  // srg_create: HIP runtime / device init vs the library's own
     // packet-event batches (events.hip.h): key / index ping-pong buffers, tile histograms
     DevBuf b_ek0, b_ek1, b_eh0, b_eh1, b_ei0, b_ei1, b_ehist, b_eoffs, b_ered;
+    // routes (routes.hip.h): in-edge lists, walk state, hop counts / offsets, query order, nonzero pairs
+    DevBuf b_rt_off, b_rt_cur, b_rt_ce, b_rt_cu, b_rt_cl, b_rt_cp, b_rt_self, b_rt_state, b_rt_hops, b_rt_offs, b_rt_idx, b_rt_perm,
+        b_rt_keys, b_rt_tmp, b_rt_pairs, b_rt_nsel;
     // Teardown.  The body releases what depends on order; the DevBuf and Event members free
     // themselves afterwards (members are destroyed after the body), so device buffers go last.
     // Every path that deletes a context has set its device on the calling thread first:
@@ -2154,6 +2159,7 @@ struct FwOverlap {
 
 #include "dense.hip.h"
 #include "sparse_run.hip.h"
+#include "routes.hip.h"
 
 void compute_device(srg_ctx& c, const DevGraph& g, const uint32_t* nodes, uint32_t n, uint64_t* out_lat,
                     float* out_loss, hipStream_t st, srg_stats* stats, HostSink* sink = nullptr,
@@ -4162,6 +4168,43 @@ int srg_event_queues_pop_device(srg_event_queues* q, uint64_t until_ns, uint64_t
         HIP_CHECK(hipStreamSynchronize(st));
         if (res) res->ms_total = ms_since(t0);
     });
+}
+
+int srg_trace_routes_device(srg_ctx* ctx, const srg_edge_list* g, const srg_path_table_dev* t, const uint32_t* src,
+                            const uint32_t* dst, uint64_t num_pairs, uint64_t hop_capacity, uint64_t* out_off,
+                            uint32_t* out_edge, uint32_t* out_vertex, void* hip_stream, srg_route_result* res,
+                            char* errbuf, size_t errlen) {
+    if (!ctx || !g || !t || (num_pairs && (!src || !dst)) || (hop_capacity && (!out_off || !out_edge))) {
+        set_err(errbuf, errlen, "null argument");
+        return SRG_ERR_ARG;
+    }
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    auto t0 = std::chrono::steady_clock::now();
+    const int rc = guard(errbuf, errlen, [&]() {
+        HIP_CHECK(hipSetDevice(ctx->device));
+        hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+        trace_routes_device(*ctx, g, t, src, dst, num_pairs, hop_capacity, out_off, out_edge, out_vertex, st, res);
+    });
+    if (res) res->ms_total = ms_since(t0);
+    return rc;
+}
+
+int srg_link_loads_device(srg_ctx* ctx, const srg_edge_list* g, const srg_path_table_dev* t, const uint64_t* counts,
+                          uint64_t* edge_packets, void* hip_stream, srg_route_result* res, char* errbuf,
+                          size_t errlen) {
+    if (!ctx || !g || !t || (g->num_vertices && !counts) || (g->num_edges && !edge_packets)) {
+        set_err(errbuf, errlen, "null argument");
+        return SRG_ERR_ARG;
+    }
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    auto t0 = std::chrono::steady_clock::now();
+    const int rc = guard(errbuf, errlen, [&]() {
+        HIP_CHECK(hipSetDevice(ctx->device));
+        hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+        link_loads_device(*ctx, g, t, counts, edge_packets, st, res);
+    });
+    if (res) res->ms_total = ms_since(t0);
+    return rc;
 }
 
 int srg_next_window(uint64_t min_next_event_ns, uint64_t runahead_ns, uint64_t end_time_ns, uint64_t* window_start_ns,
