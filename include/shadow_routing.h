@@ -249,6 +249,9 @@ void srg_destroy(srg_ctx* ctx);
                                      * mirror's step limit, the largest V of the LDS fold) come from
                                      * srg_internal_loss_limits (csrc/internal.h), and the environment switch
                                      * SRG_LOSS_ROWS_MAX_V (csrc/env_switches.h) lowers the last one */
+#define SRG_OPT_ROUTE_TREE_ROWS 44   /* source rows per batch of srg_route_trees_device and
+                                     * srg_link_loads_trees_device; 0 (default) = as many as a fixed workspace
+                                     * budget of 4 GiB allows (the bytes per row are listed with the two calls) */
 #define SRG_LOSS_NONE 0
 #define SRG_LOSS_ROWS_LDS 1
 #define SRG_LOSS_GLOBAL_ENTRIES 2
@@ -611,6 +614,60 @@ int srg_link_loads_device(srg_ctx* ctx, const srg_edge_list* graph_dev, const sr
                           const uint64_t* packet_counts_dev /* [n*n] by position */,
                           uint64_t* edge_packets_dev /* [num_edges], NOT cleared: accumulated, saturating */,
                           void* hip_stream, srg_route_result* result, char* errbuf, size_t errlen);
+
+/* ---- route trees: predecessor, hop and first-hop tables; link loads by tree -------------------
+ * For one source s the routes above to all targets form a tree: the tie rule makes every route
+ * unique, and the route to t through u ends with the route to u.  The two calls below work on whole
+ * source rows of that tree where the two above walk one pair at a time.
+ *   Essential in-edges.  A route edge (u, t) is itself a shortest path u -> t, so only edges with
+ *   lat(e) == D[u][t] can match; on a shortest-path table that filter removes no candidate of any
+ *   row and leaves the tie rule's minimum unchanged.  The filter reads the entries (u, t) of EVERY
+ *   row an edge starts from, requested or not: it trusts them.  An edge with lat(e) < D[u][t]
+ *   proves that the table is not this graph's.
+ *   Batches.  Rows are processed in batches (SRG_OPT_ROUTE_TREE_ROWS); by default a batch is as
+ *   many rows as a workspace budget of 4 GiB allows (per table entry of a batch: 16 B of doubling
+ *   scratch when n > 4096; srg_route_trees_device 4 B more when out_pred_vertex_dev is NULL;
+ *   srg_link_loads_trees_device 12 B more).  The workspace is the context's.
+ *   Which call for loads.  Measured on an MI355X on the 10 000-vertex bench table (DESIGN.md
+ *   §11.1): the tree call takes 257 ms whether 10^6, 10^7 or all 10^8 entries are nonzero (its
+ *   cost is per row holding a nonzero, 26 us each there), the pairwise call 495 ms for 10^6 and
+ *   4 463 ms for 10^7 nonzero pairs (0.45 - 0.49 us per pair).  Prefer this call from some tens of
+ *   nonzero pairs per nonzero row (about 55 on that table), srg_link_loads_device for a sparser
+ *   table or a few rows, and this call whenever n * n >= 2^31 - 1.                              */
+#define SRG_ROUTE_NONE 0xFFFFFFFFu   /* no edge / no vertex (the source's own column) */
+
+/* The route tree of each listed source, from the table and the graph alone (same rule, same tie
+ * rule, same table-shape requirements as srg_trace_routes_device).  Row i belongs to source
+ * sources_dev[i] (NULL: source i; then num_sources <= n); duplicates allowed.  For column t != s:
+ *   pred_edge   = the route's last edge (into t), pred_vertex = the vertex it comes from,
+ *   hops        = the route's length, first_edge = the route's first edge (out of s).
+ * Column t == s: SRG_ROUTE_NONE, hops 0 (the self-loop route stays with srg_trace_routes_device).
+ * result: num_pairs = num_sources * (n - 1), total_hops, max_hops over all of them; bad_pair =
+ * i * n + t (i the row index) of the smallest entry no in-edge explains (SRG_ERR_ROUTE), or
+ * u * n + t of an edge (u, t) whose latency is below the table's entry (u, t) (SRG_ERR_ROUTE too),
+ * else UINT64_MAX.  SRG_ERR_ARG: what the table-shape rules refuse, a source >= n, num_sources > 0
+ * with out_pred_edge_dev NULL, a zero-latency edge between two vertices, an endpoint >= n.
+ * num_sources == 0 is SRG_OK and touches nothing.  The four arrays are pure outputs: on any error
+ * their contents are unspecified.  Returns after its stream work is complete.                  */
+int srg_route_trees_device(srg_ctx* ctx, const srg_edge_list* graph_dev, const srg_path_table_dev* table,
+                           const uint32_t* sources_dev, uint32_t num_sources,
+                           uint32_t* out_pred_edge_dev   /* [num_sources * n] */,
+                           uint32_t* out_pred_vertex_dev /* may be NULL */,
+                           uint32_t* out_hops_dev        /* may be NULL */,
+                           uint32_t* out_first_edge_dev  /* may be NULL */,
+                           void* hip_stream, srg_route_result* result, char* errbuf, size_t errlen);
+
+/* srg_link_loads_device's contract and results, computed per source row through the route tree;
+ * no limit on n * n.  Every row holding a nonzero count gets its tree; the counts are pushed from
+ * the deepest level up (the load of the edge into t is the count of the subtree under t, the sums
+ * saturating like the loads).  Only vertices on the route of a nonzero pair have to be explained.
+ * Every batch is validated before anything is committed: any error leaves edge_packets_dev
+ * untouched.  Should the essential lists not explain a nonzero pair, or an edge lie below its
+ * entry, the call repeats itself with the full in-edge lists, so it fails exactly where
+ * srg_link_loads_device does.  A tree of depth d costs d sweeps over its row: a chain is slow.  */
+int srg_link_loads_trees_device(srg_ctx* ctx, const srg_edge_list* graph_dev, const srg_path_table_dev* table,
+                                const uint64_t* packet_counts_dev, uint64_t* edge_packets_dev,
+                                void* hip_stream, srg_route_result* result, char* errbuf, size_t errlen);
 
 /* Library build/version string. */
 const char* srg_version(void);

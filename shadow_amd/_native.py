@@ -60,6 +60,8 @@ SRG_OPT_SCAN_MIRROR = 40
 SRG_OPT_SCAN_MIRRORED = 41
 SRG_OPT_SCAN_MIRROR_CAP = 42
 SRG_OPT_LOSS_KIND = 43
+SRG_OPT_ROUTE_TREE_ROWS = 44
+SRG_ROUTE_NONE = 0xFFFFFFFF
 SRG_LOSS_NONE = 0
 SRG_LOSS_ROWS_LDS = 1
 SRG_LOSS_GLOBAL_ENTRIES = 2
@@ -234,7 +236,7 @@ EXPORTS = [
     "srg_send_packets_device", "srg_routing_info_key_tables", "srg_routing_info_add_packet_counts",
     "srg_event_queues_create", "srg_event_queues_destroy", "srg_event_queues_merge_tile",
     "srg_event_queues_push_device", "srg_event_queues_pop_device", "srg_next_window",
-    "srg_trace_routes_device", "srg_link_loads_device",
+    "srg_trace_routes_device", "srg_link_loads_device", "srg_route_trees_device", "srg_link_loads_trees_device",
 ]
 
 _lib = None
@@ -348,6 +350,12 @@ def lib():
     L.srg_link_loads_device.argtypes = [
         c.c_void_p, c.POINTER(EdgeList), c.POINTER(PathTableDev), c.c_void_p, c.c_void_p, c.c_void_p,
         c.POINTER(RouteResult), c.c_char_p, c.c_size_t]
+    L.srg_route_trees_device.restype = c.c_int
+    L.srg_route_trees_device.argtypes = [
+        c.c_void_p, c.POINTER(EdgeList), c.POINTER(PathTableDev), c.c_void_p, c.c_uint32, c.c_void_p, c.c_void_p,
+        c.c_void_p, c.c_void_p, c.c_void_p, c.POINTER(RouteResult), c.c_char_p, c.c_size_t]
+    L.srg_link_loads_trees_device.restype = c.c_int
+    L.srg_link_loads_trees_device.argtypes = list(L.srg_link_loads_device.argtypes)
     L.srg_routing_info_build.restype = c.c_int
     L.srg_routing_info_build.argtypes = [c.c_void_p, c.POINTER(EdgeList), c.c_void_p, c.c_uint32, c.c_int,
                                          c.POINTER(c.c_void_p), c.POINTER(Stats), c.c_char_p, c.c_size_t]

@@ -77,6 +77,22 @@ static inline unsigned loss_rows_max_v(unsigned limit) {
     if (end == e || *end) return limit;  // not a number: ignored
     return v < limit ? (unsigned)v : limit;
 }
+// [A/B] SRG_ROUTE_TREE_GROUP=16 / 64: the route trees' predecessor kernel with 16 lanes or a wave per target
+// (route_trees.hip.h); 0 = unset: chosen by the average list length
+static inline int route_tree_group() {
+    return equals("SRG_ROUTE_TREE_GROUP", "64") ? 64 : equals("SRG_ROUTE_TREE_GROUP", "16") ? 16 : 0;
+}
+// [test] SRG_ROUTE_TREE_LDS_MAX_V=n: the route trees keep a row's doubling jumps and subtree sums in LDS
+// only for V <= n, so a small graph takes the global-scratch paths of a large one.  Only ever lowers
+// the limit (as SRG_LOSS_ROWS_MAX_V above).
+static inline unsigned route_tree_lds_max_v(unsigned limit) {
+    const char* e = std::getenv("SRG_ROUTE_TREE_LDS_MAX_V");
+    if (!e || !*e) return limit;
+    char* end = nullptr;
+    const unsigned long long v = std::strtoull(e, &end, 10);
+    if (end == e || *end) return limit;  // not a number: ignored
+    return v < limit ? (unsigned)v : limit;
+}
 // [A/B] SRG_CREATE_WARM=0...: srg_create skips its warm-up
 static inline bool create_warm_off() { return first_char_is("SRG_CREATE_WARM", '0'); }
 

@@ -12,7 +12,8 @@
 // (rank / XCD / scan-group splits) -- all three without HIP; dense.hip.h (run_dense) and
 // sparse_run.hip.h (run_sparse, choose_sparse), sections of this translation unit; the device
 // headers (kernels, tight_sparse, sparse, sparse_ds, events, xchg); routes.hip.h (route tracing and
-// link loads over a finished table, rule in route_rule.h), a section too.  Still here, in order: the
+// link loads over a finished table, rule in route_rule.h) and route_trees.hip.h (whole route trees and
+// loads pushed up them, rules in route_tree_rule.h), sections too.  Still here, in order: the
 // validation / W / certify / extract kernels, the context (srg_ctx), prelude(), HostSink, the FW
 // schedules (stream_hop, fw_blocked, SymFw, FwOverlap), compute_device, direct paths, packet
 // events, the H2D codec, host_entry, extern "C".
@@ -55,6 +56,7 @@
 #include "sparse_ds.hip.h"
 #include "events.hip.h"
 #include "route_rule.h"
+#include "route_tree_rule.h"
 #include "event_queue.hip.h"
 #include "xchg.hip.h"
 
@@ -855,6 +857,11 @@ struct srg_ctx {
     // routes (routes.hip.h): in-edge lists, walk state, hop counts / offsets, query order, nonzero pairs
     DevBuf b_rt_off, b_rt_cur, b_rt_ce, b_rt_cu, b_rt_cl, b_rt_cp, b_rt_self, b_rt_state, b_rt_hops, b_rt_offs, b_rt_idx, b_rt_perm,
         b_rt_keys, b_rt_tmp, b_rt_pairs, b_rt_nsel;
+    // route trees (route_trees.hip.h): essential in-edge lists, state, a batch's predecessors, hops, doubling /
+    // subtree scratch, deepest level per row, the rows with a nonzero count
+    DevBuf b_rtt_off, b_rtt_cur, b_rtt_ce, b_rtt_cu, b_rtt_cl, b_rtt_cp, b_rtt_self, b_rtt_state, b_rtt_tmp, b_rtt_pe, b_rtt_pv,
+        b_rtt_hops, b_rtt_scr, b_rtt_rowmax, b_rtt_rownnz, b_rtt_active, b_rtt_nsel;
+    int route_tree_rows = 0;            // source rows per batch of the route-tree calls, 0 = by budget (SRG_OPT_ROUTE_TREE_ROWS)
     // Teardown.  The body releases what depends on order; the DevBuf and Event members free
     // themselves afterwards (members are destroyed after the body), so device buffers go last.
     // Every path that deletes a context has set its device on the calling thread first:
@@ -2160,6 +2167,7 @@ struct FwOverlap {
 #include "dense.hip.h"
 #include "sparse_run.hip.h"
 #include "routes.hip.h"
+#include "route_trees.hip.h"
 
 void compute_device(srg_ctx& c, const DevGraph& g, const uint32_t* nodes, uint32_t n, uint64_t* out_lat,
                     float* out_loss, hipStream_t st, srg_stats* stats, HostSink* sink = nullptr,
@@ -3577,6 +3585,10 @@ int srg_set_option(srg_ctx* ctx, int option, double value) {
             if (!(value >= 0 && value <= 1073741824.0)) return SRG_ERR_ARG;
             ctx->scan_mirror_cap = (int)value;
             return SRG_OK;
+        case SRG_OPT_ROUTE_TREE_ROWS:
+            if (!(value >= 0 && value <= 1073741824.0)) return SRG_ERR_ARG;
+            ctx->route_tree_rows = (int)value;
+            return SRG_OK;
         case SRG_OPT_TABLE_POOL_BYTES: {
             if (!(value >= 0.0 && value <= 1e15)) return SRG_ERR_ARG;
             std::lock_guard<std::mutex> pl(ctx->tpool->mu);
@@ -3634,6 +3646,7 @@ int srg_get_option(srg_ctx* ctx, int option, double* value) {
         case SRG_OPT_SCAN_MIRRORED: *value = ctx->scan_mirrored; break;
         case SRG_OPT_SCAN_MIRROR_CAP: *value = ctx->scan_mirror_cap; break;
         case SRG_OPT_LOSS_KIND: *value = ctx->loss_kind; break;
+        case SRG_OPT_ROUTE_TREE_ROWS: *value = ctx->route_tree_rows; break;
         default: return SRG_ERR_ARG;
     }
     return SRG_OK;
@@ -4202,6 +4215,44 @@ int srg_link_loads_device(srg_ctx* ctx, const srg_edge_list* g, const srg_path_t
         HIP_CHECK(hipSetDevice(ctx->device));
         hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
         link_loads_device(*ctx, g, t, counts, edge_packets, st, res);
+    });
+    if (res) res->ms_total = ms_since(t0);
+    return rc;
+}
+
+int srg_route_trees_device(srg_ctx* ctx, const srg_edge_list* g, const srg_path_table_dev* t, const uint32_t* sources,
+                           uint32_t num_sources, uint32_t* out_pred_edge, uint32_t* out_pred_vertex, uint32_t* out_hops,
+                           uint32_t* out_first_edge, void* hip_stream, srg_route_result* res, char* errbuf,
+                           size_t errlen) {
+    if (!ctx || !g || !t || (num_sources && !out_pred_edge)) {
+        set_err(errbuf, errlen, "null argument");
+        return SRG_ERR_ARG;
+    }
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    auto t0 = std::chrono::steady_clock::now();
+    const int rc = guard(errbuf, errlen, [&]() {
+        HIP_CHECK(hipSetDevice(ctx->device));
+        hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+        route_trees_device(*ctx, g, t, sources, num_sources, out_pred_edge, out_pred_vertex, out_hops, out_first_edge,
+                           st, res);
+    });
+    if (res) res->ms_total = ms_since(t0);
+    return rc;
+}
+
+int srg_link_loads_trees_device(srg_ctx* ctx, const srg_edge_list* g, const srg_path_table_dev* t,
+                                const uint64_t* counts, uint64_t* edge_packets, void* hip_stream, srg_route_result* res,
+                                char* errbuf, size_t errlen) {
+    if (!ctx || !g || !t || (g->num_vertices && !counts) || (g->num_edges && !edge_packets)) {
+        set_err(errbuf, errlen, "null argument");
+        return SRG_ERR_ARG;
+    }
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    auto t0 = std::chrono::steady_clock::now();
+    const int rc = guard(errbuf, errlen, [&]() {
+        HIP_CHECK(hipSetDevice(ctx->device));
+        hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+        link_loads_trees_device(*ctx, g, t, counts, edge_packets, st, res);
     });
     if (res) res->ms_total = ms_since(t0);
     return rc;

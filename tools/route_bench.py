@@ -5,6 +5,13 @@ table built once by srg_compute_shortest_paths_device and kept in HBM.  One proc
        lists of 5 * 10^7 edges are rebuilt on every call)
   (a)  srg_trace_routes_device of `--pairs` (10^6) random pairs, hop arrays sized beforehand
   (b)  srg_link_loads_device for a counts table with `--loads` (10^6, 10^7) nonzero pairs
+  (d)  srg_route_trees_device of all sources, all four outputs, with 16 lanes per target and with a
+       wave per target (SRG_ROUTE_TREE_GROUP, read on every call), alternating
+  (e)  srg_link_loads_trees_device for the same counts tables as (b), checked equal to (b)'s loads
+       and result, and for a fully nonzero table (which (b) is not timed on)
+  and the essential fraction of arcs: those with lat(e) == D[u][t], which (d) and (e) keep.  Their
+  byte model: rows x essential arcs x 20 B (an entry's endpoint and latency plus the gather D[s][u];
+  only the few entries whose latency fits read more)
 
 Each variant: `--warmup` (2) calls, then `--reps` (7) timed ones; every call returns after its stream
 synchronise and is timed with a host clock.  Median, min and max go out as one JSON line.
@@ -28,6 +35,9 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 ENTRY_BYTES = 32
+# the tree kernels test an entry's latency first: endpoint 4 + latency 8 read in sequence and the
+# gather D[s][u] 8; the few entries that pass also read the loss, the edge index and L[s][u]
+TREE_ENTRY_BYTES = 20
 HBM_BYTES_PER_S = 8.0e12
 
 
@@ -102,15 +112,69 @@ def main():
     progress("c_trace_one_pair")
     out["a_trace_pairs"] = trace_variant(args.pairs)
     progress("a_trace_pairs")
+    count_idx, count_val, pairwise = {}, {}, {}
     for nnz in args.loads:
         counts = torch.zeros(V * V, dtype=torch.int64, device=dev)
-        idx = torch.from_numpy(rng.choice(V * V, nnz, replace=False)).to(dev)
-        counts[idx] = torch.from_numpy(rng.integers(1, 1000, nnz, dtype=np.int64)).to(dev)
-        del idx
+        count_idx[nnz] = torch.from_numpy(rng.choice(V * V, nnz, replace=False))
+        count_val[nnz] = torch.from_numpy(rng.integers(1, 1000, nnz, dtype=np.int64))
+        counts[count_idx[nnz].to(dev)] = count_val[nnz].to(dev)
         loads = torch.zeros(e.num_edges, dtype=torch.int64, device=dev)
         stat, res = timed(lambda: routes.link_loads_device(router, dg, table, counts, loads))
         out[f"b_link_loads_{nnz}"] = {**stat, "model": model(stat, res, 2)}
         progress(f"b_link_loads_{nnz}")
+        pairwise[nnz] = (loads, res)
+        del counts
+
+    # the essential fraction: arcs u -> t (both orientations of an undirected edge, no self-loops)
+    # whose latency equals the table entry (u, t)
+    arc = dg.src != dg.dst
+    es, ed, el = dg.src[arc].long(), dg.dst[arc].long(), dg.lat[arc]
+    ess = int((lat[es, ed] == el).sum())
+    arcs = int(arc.sum())
+    if not e.directed:
+        ess += int((lat[ed, es] == el).sum())
+        arcs *= 2
+    out["essential_arcs"] = {"arcs": arcs, "essential": ess, "fraction": round(ess / max(arcs, 1), 6)}
+    del es, ed, el, arc
+
+    def tree_model(stat, rows):
+        entries = rows * ess  # every row examines every essential arc once
+        b = entries * TREE_ENTRY_BYTES
+        return {"rows": rows, "entries_examined": entries, "entry_bytes": TREE_ENTRY_BYTES, "bytes": b,
+                "bytes_per_s": round(b / (stat["median_ms"] * 1e-3), 1),
+                "hbm_fraction": round(b / (stat["median_ms"] * 1e-3) / HBM_BYTES_PER_S, 4)}
+
+    outs = [torch.empty(V * V, dtype=torch.int32, device=dev) for _ in range(4)]
+    for rep in range(2):  # (alternating: other work shares the machine)
+        for group in ("16", "64"):
+            os.environ["SRG_ROUTE_TREE_GROUP"] = group
+            stat, res = timed(lambda: routes.route_trees_device(router, dg, table, None, V, *outs))
+            key = f"d_route_trees_all_group{group}_run{rep}"
+            out[key] = {**stat, "total_hops": int(res["total_hops"]), "max_hops": int(res["max_hops"]),
+                        "model": tree_model(stat, V)}
+            progress(key)
+    del outs
+    os.environ.pop("SRG_ROUTE_TREE_GROUP", None)
+
+    for nnz in list(args.loads) + [V * V]:
+        if nnz < V * V:
+            counts = torch.zeros(V * V, dtype=torch.int64, device=dev)
+            counts[count_idx[nnz].to(dev)] = count_val[nnz].to(dev)
+        else:
+            counts = torch.from_numpy(rng.integers(1, 1000, V * V, dtype=np.int64)).to(dev)
+        loads = torch.zeros(e.num_edges, dtype=torch.int64, device=dev)
+        stat, res = timed(lambda: routes.link_loads_trees_device(router, dg, table, counts, loads))
+        rows = int((counts.view(V, V) != 0).any(dim=1).sum())
+        key = f"e_tree_loads_{nnz}"
+        out[key] = {**stat, "pairs": int(res["num_pairs"]), "total_hops": int(res["total_hops"]),
+                    "max_hops": int(res["max_hops"]), "model": tree_model(stat, rows)}
+        if nnz in pairwise:
+            # both accumulated the same number of calls onto zeros: the loads must be equal
+            pl, pres = pairwise[nnz]
+            out[key]["equals_pairwise"] = bool(torch.equal(pl, loads)) and all(
+                res[k] == pres[k] for k in ("num_pairs", "total_hops", "max_hops", "bad_pair"))
+            out[key]["speedup_vs_pairwise"] = round(out[f"b_link_loads_{nnz}"]["median_ms"] / stat["median_ms"], 2)
+        progress(key)
         del counts, loads
 
     line = json.dumps(out)
