@@ -21,8 +21,6 @@ bool run_dense(srg_ctx& c, const DevGraph& g, const Plan& pl, const uint32_t* no
     const size_t VV = Vp * Vp;
     const bool multi = c.comm && c.comm->nranks > 1;
     Timer tm(st);
-    c.own_row0 = pl.p0;  // this rank's output rows (the host entry ships only these without the exchange)
-    c.own_row1 = pl.p1;
 
     K* W = (K*)c.b_W.get(VV * sizeof(K));
     uint32_t* WL = (uint32_t*)c.b_WL.get(VV * 4);
@@ -153,12 +151,8 @@ bool run_dense(srg_ctx& c, const DevGraph& g, const Plan& pl, const uint32_t* no
     const bool exchange = multi && c.gather_output;
     auto exchange_rows = [&](void* out, size_t elem) {  // on cs, after st
         const size_t row = (size_t)n * elem;
-        std::vector<size_t> offs(pl.G), lens(pl.G);
-        for (int r = 0; r < pl.G; ++r) {
-            const size_t a = (uint64_t)n * r / pl.G, b = (uint64_t)n * (r + 1) / pl.G;
-            offs[r] = a * row;
-            lens[r] = (b - a) * row;
-        }
+        std::vector<size_t> offs, lens;
+        slice_tables(n, pl.G, row, offs, lens);
         cs_after_st();
         c.comm->allgatherv(out, offs.data(), lens.data(), cs);
     };

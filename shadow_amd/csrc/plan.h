@@ -7,6 +7,8 @@
 #include <cstdint>
 #include <vector>
 
+#include "entry_plan.h"
+
 namespace {
 
 // ---- distribution plan --------------------------------------------------
@@ -41,9 +43,9 @@ inline Plan make_plan(int G, int g, uint32_t V, int T, const std::vector<uint32_
     p.blk_lo[G] = p.nb;
     p.rb0 = p.blk_lo[g];
     p.rb1 = p.blk_lo[g + 1];
-    const uint64_t n = nodes_h.size();
-    p.p0 = (uint32_t)(n * g / G);
-    p.p1 = (uint32_t)(n * (g + 1) / G);
+    const Range own = rank_rows(nodes_h.size(), g, G);
+    p.p0 = (uint32_t)own.lo;
+    p.p1 = (uint32_t)own.hi;
     for (uint32_t q = p.p0; q < p.p1; ++q) {
         p.lnodes.push_back(nodes_h[q]);
         p.lpos.push_back(q);

@@ -9,14 +9,16 @@
 //   sparse (run_sparse)  batched delta-stepping + loss fold (k_sparse_ds), or the lexicographic
 //                        Bellman-Ford sweeps (k_sparse_bf) for u64 labels
 // Files: env_switches.h (every SRG_* environment switch), host_pool.h (host worker pool), plan.h
-// (rank / XCD / scan-group splits) -- all three without HIP; dense.hip.h (run_dense) and
-// sparse_run.hip.h (run_sparse, choose_sparse), sections of this translation unit; the device
-// headers (kernels, tight_sparse, sparse, sparse_ds, events, xchg); routes.hip.h (route tracing and
-// link loads over a finished table, rule in route_rule.h) and route_trees.hip.h (whole route trees and
-// loads pushed up them, rules in route_tree_rule.h), sections too.  Still here, in order: the
-// validation / W / certify / extract kernels, the context (srg_ctx), prelude(), HostSink, the FW
-// schedules (stream_hop, fw_blocked, SymFw, FwOverlap), compute_device, direct paths, packet
-// events, the H2D codec, host_entry, extern "C".
+// (rank / XCD / scan-group splits), entry_plan.h (the rank row / edge split, the host entry's
+// flags) -- all four without HIP; dense.hip.h (run_dense) and sparse_run.hip.h (run_sparse,
+// choose_sparse), sections of this translation unit; the device headers (kernels, tight_sparse,
+// sparse, sparse_ds, events, xchg); routes.hip.h (route tracing and link loads over a finished
+// table, rule in route_rule.h) and route_trees.hip.h (whole route trees and loads pushed up them,
+// rules in route_tree_rule.h), sections too; h2d_codec.hip.h (the host entry's plain copy, H2D
+// codec and late-loss thread) and host_entry.hip.h (the host entry, stage by stage), the last two
+// sections.  Still here, in order: the validation / W / certify / extract kernels, the context
+// (srg_ctx), prelude(), HostSink, the FW schedules (stream_hop, fw_blocked, SymFw, FwOverlap),
+// compute_device, direct paths, packet events, the event queues, guard(), extern "C".
 // No CPU fallback: every entry point fails loudly (status code) when HIP is unavailable.
 #include <hip/hip_runtime.h>
 #include <hsa/hsa.h>
@@ -794,7 +796,6 @@ struct srg_ctx {
     std::vector<std::vector<uint32_t>> codec_ex;  // its per-worker exception lists
     std::vector<uint32_t> slice_exc;    // the slice's exceptions (global index, src, dst), all chunks
     DevBuf b_xexc;                      // edge-sharded exchange: every rank's exceptions, counts
-    size_t own_row0 = 0, own_row1 = ~(size_t)0;  // the output rows this rank routed (multi-rank: [p0, p1))
     int late_loss = 1;               // host entry: edge losses shipped beside FW (SRG_OPT_LATE_LOSS)
     hipStream_t loss_stream = nullptr;  // = d2h_stream (see srg_create)
     Event ev_ledges, ev_lin, ev_ldone, ev_wlate;
@@ -2598,325 +2599,7 @@ void evq_pop(srg_event_queues& q, uint64_t until, uint64_t capacity, uint64_t* o
     evq_fill_result(q, total, res);
 }
 
-__global__ void k_widen_edges(size_t n, const uint16_t* __restrict__ s16, const uint16_t* __restrict__ d16,
-                              const uint32_t* __restrict__ l32, uint32_t* __restrict__ src, uint32_t* __restrict__ dst,
-                              uint64_t* __restrict__ lat) {
-    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        src[i] = s16[i];
-        dst[i] = d16[i];
-        lat[i] = l32[i];
-    }
-}
-
-// H2D codec of the host entry (SRG_OPT_H2D_CODEC): the edge list crosses PCIe narrowed -- u16
-// endpoints (V <= 65536) and u32 latencies -- 12 B instead of 20 B per edge, then is widened on
-// the device.  Host threads narrow chunk i+1 into a page-locked ring while chunk i is in flight.
-// Returns false (nothing usable staged) when an endpoint >= 65536 or a latency >= 2^32 is seen:
-// the caller then ships the plain arrays, whose checks report such edges as the reference does.
-// on_chunk(e0, ne, exc, nexc, last): edges [e0, e0 + ne) are decoded on the device (in st order); exc =
-// their exceptions (global index, src, dst) when the chunk went sequential-pair, else null
-using ChunkFn = std::function<void(size_t, size_t, const uint32_t*, size_t, bool)>;
-bool codec_in(srg_ctx& c, const srg_edge_list* g, DevGraph& dg, hipStream_t st, size_t a0, size_t a1, bool with_loss,
-              bool& all_narrow, bool& all_seq, const ChunkFn& on_chunk = nullptr);
-
-// Sequential-pair codec, device side: edge i of a chunk is (src, dst) = (es[j], ed[j] + i - ei[j])
-// for the last exception j with ei[j] <= i (ei[0] = 0: a chunk starts with one), latency = l32[i].
-// Consecutive lanes search the same few exceptions (wave-broadcast loads).
-__global__ void k_decode_seq(size_t ne, const uint32_t* __restrict__ l32, const uint32_t* __restrict__ exc, uint32_t nexc,
-                             uint32_t* __restrict__ src, uint32_t* __restrict__ dst, uint64_t* __restrict__ lat) {
-    const uint32_t* ei = exc;
-    const uint32_t* es = exc + nexc;
-    const uint32_t* ed = exc + 2 * (size_t)nexc;
-    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < ne; i += (size_t)gridDim.x * blockDim.x) {
-        uint32_t lo = 0, hi = nexc - 1;
-        while (lo < hi) {
-            const uint32_t mid = (lo + hi + 1) >> 1;
-            if (ei[mid] <= (uint32_t)i) lo = mid;
-            else hi = mid - 1;
-        }
-        src[i] = es[lo];
-        dst[i] = ed[lo] + ((uint32_t)i - ei[lo]);
-        lat[i] = l32[i];
-    }
-}
-
-// The edge-sharded exchange's sequential-pair form: edges [e0, e1) of the whole list from every
-// slice's exceptions ex = (global index, src, dst) x nexc in index order (each slice starts with
-// one, so index 0 is covered) and the u32 latencies.
-__global__ void k_decode_seq_global(size_t e0, size_t e1, const uint32_t* __restrict__ l32,
-                                    const uint32_t* __restrict__ ex, uint32_t nexc, uint32_t* __restrict__ src,
-                                    uint32_t* __restrict__ dst, uint64_t* __restrict__ lat) {
-    for (size_t i = e0 + blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < e1; i += (size_t)gridDim.x * blockDim.x) {
-        uint32_t lo = 0, hi = nexc - 1;
-        while (lo < hi) {
-            const uint32_t mid = (lo + hi + 1) >> 1;
-            if (ex[3 * (size_t)mid] <= (uint32_t)i) lo = mid;
-            else hi = mid - 1;
-        }
-        src[i] = ex[3 * (size_t)lo + 1];
-        dst[i] = ex[3 * (size_t)lo + 2] + ((uint32_t)i - ex[3 * (size_t)lo]);
-        lat[i] = l32[i];
-    }
-}
-
-template <class T>
-T* stage_in(DevBuf& b, const T* host, size_t count, hipStream_t st) {
-    T* d = (T*)b.get(std::max<size_t>(count, 1) * sizeof(T));
-    if (count) HIP_CHECK(hipMemcpyAsync(d, host, count * sizeof(T), hipMemcpyHostToDevice, st));
-    return d;
-}
-
-// Ships edges [a0, a1) into the full-length device arrays (the rank's slice when the edge list
-// is sharded, else all of it).
-// Sequential-pair mode (whole lists only; SRG_CODEC_SEQ=0 turns it off): an edge list in
-// row order -- a GML complete graph lists (i, i), (i, i+1), ... (i, V-1), then row i+1 -- needs
-// no endpoints over PCIe: an edge (s, d) following (s, d - 1) is implied, and only the others
-// (row starts, ~V of them) cross as exceptions, so a chunk is its u32 latencies (4 B per edge
-// instead of 8) plus ~12 B per row.  A chunk with more than 1/8 exceptions is re-narrowed to
-// u16 endpoints and the rest of the list stays in that mode.
-// all_narrow: every edge of the slice also stays narrowed on the device (b_n16s / b_n16d / b_n32l),
-// false when the host-slow switch shipped the rest of the slice plain.
-// all_seq: every chunk of the slice went sequential-pair: its u32 latencies are in b_n32l and its
-// exceptions (GLOBAL edge index, src, dst) in c.slice_exc -- the edge-sharded exchange then ships
-// that form (4 B per edge) instead of the u16 narrowing (8 B).
-// the host entry's codec worker pool and its page-locked rings (first use, or srg_create's warm-up)
-constexpr size_t kCodecChunk = (size_t)2 << 20;  // edges per chunk: 32 MB narrowed (+ loss)
-constexpr int kRingSlots = 3;
-void ensure_pool(srg_ctx& c) {
-    if (c.pool) return;
-    c.pool = new HostPool();
-    const unsigned hw = std::thread::hardware_concurrency();
-    int nt = (int)std::max(1u, std::min(8u, hw ? hw : 1u));
-    if (const int e = srg_env::codec_threads()) nt = e;  // experiments
-    c.pool->start(nt);
-}
-void ensure_rings(srg_ctx& c) {
-    const size_t slot = kCodecChunk * 16;
-    if (c.h_ring_bytes < slot * kRingSlots) {
-        if (c.h_ring) HIP_CHECK(hipHostFree(c.h_ring));
-        c.h_ring = nullptr;
-        c.h_ring_bytes = 0;
-        HIP_CHECK(hipHostMalloc(&c.h_ring, slot * kRingSlots, hipHostMallocDefault));
-        c.h_ring_bytes = slot * kRingSlots;
-    }
-    for (Event& e : c.ev_ring) e.create();
-    if (!c.h_lring) HIP_CHECK(hipHostMalloc(&c.h_lring, kCodecChunk * 4 * kRingSlots, hipHostMallocDefault));
-    for (Event* e : {&c.ev_lring[0], &c.ev_lring[1], &c.ev_lring[2], &c.ev_lin, &c.ev_ldone}) e->create();
-}
-
-bool codec_in(srg_ctx& c, const srg_edge_list* g, DevGraph& dg, hipStream_t st, size_t a0, size_t a1, bool with_loss,
-              bool& all_narrow, bool& all_seq, const ChunkFn& on_chunk) {
-    all_narrow = true;
-    all_seq = false;
-    c.slice_exc.clear();
-    const auto t_setup = std::chrono::steady_clock::now();
-    const size_t E = g->num_edges, A = a1 - a0;
-    constexpr size_t CE = kCodecChunk;  // edges per chunk: 32 MB narrowed (+ loss)
-    constexpr int NB = kRingSlots;      // ring slots
-    const size_t slot = CE * 16;
-    ensure_pool(c);
-    ensure_rings(c);
-    uint16_t* s16 = (uint16_t*)c.b_n16s.get(E * 2);
-    uint16_t* d16 = (uint16_t*)c.b_n16d.get(E * 2);
-    uint32_t* l32 = (uint32_t*)c.b_n32l.get(E * 4);
-    dg.src = (uint32_t*)c.b_src.get(E * 4);
-    dg.dst = (uint32_t*)c.b_dst.get(E * 4);
-    dg.lat = (uint64_t*)c.b_lat.get(E * 8);
-    dg.loss = (float*)c.b_loss.get(E * 4);
-    const double ms_setup = ms_since(t_setup);  // (first call: worker threads, pinned ring, device arrays)
-    std::atomic<bool> bad{false};     // a latency >= 2^32: the codec cannot carry the list
-    std::atomic<bool> bad_ep{false};  // an endpoint >= 65536: only the sequential-pair chunks can
-    const bool dbg = srg_env::debug_codec();
-    double t_conv = 0, t_wait = 0;
-    const size_t nch = (A + CE - 1) / CE;
-    bool seq = !srg_env::codec_seq_off();  // (a slice of a row-ordered list is row-ordered too)
-    uint32_t* dexc = seq ? (uint32_t*)c.b_exc.get(CE * 4) : nullptr;
-    const int nwk = c.pool->size();
-    if ((int)c.codec_ex.size() < nwk) c.codec_ex.resize(nwk);
-    size_t seq_chunks = 0;
-    for (size_t ch = 0; ch < nch; ++ch) {
-        const int b = (int)(ch % NB);
-        auto tw = std::chrono::steady_clock::now();
-        if (ch >= (size_t)NB) HIP_CHECK(hipEventSynchronize(c.ev_ring[b]));  // the slot's previous DMA is done
-        const size_t e0 = a0 + ch * CE, ne = std::min(CE, a1 - e0);
-        unsigned char* base = (unsigned char*)c.h_ring + (size_t)b * slot;
-        uint16_t* hs = (uint16_t*)base;
-        uint16_t* hd = hs + CE;
-        uint32_t* hl = (uint32_t*)(hd + CE);
-        float* hb = (float*)(hl + CE);
-        auto tc = std::chrono::steady_clock::now();
-        t_wait += std::chrono::duration<double, std::milli>(tc - tw).count();
-        std::atomic<bool> dense{false};
-        const bool seq_ch = seq;
-        c.pool->run([&](int w, int nw) {
-            const size_t a = ne * w / nw, z = ne * (w + 1) / nw;
-            const uint32_t* src = g->src + e0;
-            const uint32_t* dst = g->dst + e0;
-            const uint64_t* lat = g->latency_ns + e0;
-            uint32_t orx = 0;
-            uint64_t orl = 0;
-            if (seq_ch) {
-                std::vector<uint32_t>& ex = c.codec_ex[w];
-                ex.clear();
-                if (!seq_encode_slice(src, dst, lat, hl, a, z, ex, 3 * ((z - a) / 8 + 1), orx, orl))
-                    dense.store(true, std::memory_order_relaxed);  // (redone below with u16 endpoints)
-            } else {
-                for (size_t i = a; i < z; ++i) {
-                    const uint32_t x = src[i], y = dst[i];
-                    const uint64_t l = lat[i];
-                    orx |= x | y;
-                    orl |= l;
-                    hs[i] = (uint16_t)x;
-                    hd[i] = (uint16_t)y;
-                    hl[i] = (uint32_t)l;
-                }
-            }
-            if (with_loss) std::memcpy(hb + a, g->packet_loss + e0 + a, (z - a) * 4);  // f32 as is
-            if (orl >> 32) bad.store(true, std::memory_order_relaxed);
-            if (orx >> 16) bad_ep.store(true, std::memory_order_relaxed);
-        });
-        // sequential-pair chunks never carry u16 endpoints (exceptions are u32): only the u16
-        // narrowing needs every endpoint below 65536
-        if (seq_ch && dense.load() && bad_ep.load()) bad.store(true);
-        if (seq_ch && dense.load() && !bad.load()) {
-            // not a row-ordered list: this chunk's endpoints narrowed after all, u16 from here on
-            seq = false;
-            c.pool->run([&](int w, int nw) {
-                const size_t a = ne * w / nw, z = ne * (w + 1) / nw;
-                for (size_t i = a; i < z; ++i) {
-                    hs[i] = (uint16_t)g->src[e0 + i];
-                    hd[i] = (uint16_t)g->dst[e0 + i];
-                }
-            });
-        }
-        const bool chunk_seq = seq_ch && !dense.load();
-        if (!chunk_seq && bad_ep.load()) bad.store(true);
-        const double dt = ms_since(tc);
-        t_conv += dt;
-        if (bad.load()) {
-            HIP_CHECK(hipStreamSynchronize(st));  // no DMA may still read the ring
-            return false;
-        }
-        // the host is busy (narrowing takes longer than shipping the chunks plain would at ~55 GB/s):
-        // the remaining edges go plain, straight from the caller's arrays.  Judged on the average over
-        // the chunks so far, past the first, with a 1.5x margin: shipping plain also gives up the FW
-        // beside the H2D (~5 ms at C3), and a single chunk slowed by the caller's fresh table being
-        // faulted in beside it (0.79 ms against 0.76) switched a C3 first call over (round 6)
-        const double plain_ms = (double)ne * 20.0 / 55e9 * 1e3;
-        bool slow = ch + 1 < nch && ch >= 1 && t_conv / (double)(ch + 1) > 1.5 * plain_ms;
-        if (size_t k = 0; srg_env::codec_slow_after(k)) slow = ch + 1 < nch && ch >= k;  // tests
-        if (chunk_seq) {
-            // the workers' exception lists, in order, as SoA (index | src | dst) where the u16
-            // endpoints would have gone
-            size_t nexc = 0;
-            for (int w = 0; w < nwk; ++w) nexc += c.codec_ex[w].size() / 3;
-            uint32_t* hx = (uint32_t*)hs;
-            size_t q = 0;
-            const size_t x0 = c.slice_exc.size();
-            for (int w = 0; w < nwk; ++w) {
-                const std::vector<uint32_t>& ex = c.codec_ex[w];
-                for (size_t k = 0; k + 2 < ex.size(); k += 3, ++q) {
-                    hx[q] = ex[k];
-                    hx[nexc + q] = ex[k + 1];
-                    hx[2 * nexc + q] = ex[k + 2];
-                    c.slice_exc.push_back((uint32_t)(e0 + ex[k]));  // global index, src, dst
-                    c.slice_exc.push_back(ex[k + 1]);
-                    c.slice_exc.push_back(ex[k + 2]);
-                }
-            }
-            HIP_CHECK(hipMemcpyAsync(l32 + e0, hl, ne * 4, hipMemcpyHostToDevice, st));
-            HIP_CHECK(hipMemcpyAsync(dexc, hx, nexc * 12, hipMemcpyHostToDevice, st));
-            if (with_loss) HIP_CHECK(hipMemcpyAsync((float*)dg.loss + e0, hb, ne * 4, hipMemcpyHostToDevice, st));
-            HIP_CHECK(hipEventRecord(c.ev_ring[b], st));
-            k_decode_seq<<<grid_for(ne), kThreads, 0, st>>>(ne, l32 + e0, dexc, (uint32_t)nexc, (uint32_t*)dg.src + e0,
-                                                             (uint32_t*)dg.dst + e0, (uint64_t*)dg.lat + e0);
-            ++seq_chunks;
-            if (on_chunk) on_chunk(e0, ne, c.slice_exc.data() + x0, nexc, ch + 1 == nch && !slow);
-        } else {
-            HIP_CHECK(hipMemcpyAsync(s16 + e0, hs, ne * 2, hipMemcpyHostToDevice, st));
-            HIP_CHECK(hipMemcpyAsync(d16 + e0, hd, ne * 2, hipMemcpyHostToDevice, st));
-            HIP_CHECK(hipMemcpyAsync(l32 + e0, hl, ne * 4, hipMemcpyHostToDevice, st));
-            if (with_loss) HIP_CHECK(hipMemcpyAsync((float*)dg.loss + e0, hb, ne * 4, hipMemcpyHostToDevice, st));
-            HIP_CHECK(hipEventRecord(c.ev_ring[b], st));
-            k_widen_edges<<<grid_for(ne), kThreads, 0, st>>>(ne, s16 + e0, d16 + e0, l32 + e0, (uint32_t*)dg.src + e0,
-                                                              (uint32_t*)dg.dst + e0, (uint64_t*)dg.lat + e0);
-            if (on_chunk) on_chunk(e0, ne, nullptr, 0, ch + 1 == nch && !slow);
-        }
-        HIP_CHECK(hipGetLastError());
-        if (slow) {
-            const size_t r0 = e0 + ne, rn = a1 - r0;
-            HIP_CHECK(hipMemcpyAsync((uint32_t*)dg.src + r0, g->src + r0, rn * 4, hipMemcpyHostToDevice, st));
-            HIP_CHECK(hipMemcpyAsync((uint32_t*)dg.dst + r0, g->dst + r0, rn * 4, hipMemcpyHostToDevice, st));
-            HIP_CHECK(hipMemcpyAsync((uint64_t*)dg.lat + r0, g->latency_ns + r0, rn * 8, hipMemcpyHostToDevice, st));
-            if (with_loss)
-                HIP_CHECK(hipMemcpyAsync((float*)dg.loss + r0, g->packet_loss + r0, rn * 4, hipMemcpyHostToDevice, st));
-            if (dbg) std::fprintf(stderr, "codec: host slow after chunk %zu (%.2f ms), rest plain\n", ch, dt);
-            if (on_chunk) on_chunk(r0, rn, nullptr, 0, true);
-            all_narrow = false;
-            break;
-        }
-    }
-    if (seq_chunks) all_narrow = false;  // (the endpoints are not on the device narrowed)
-    all_seq = seq_chunks == nch && nch > 0;
-    if (dbg) std::fprintf(stderr, "codec: %zu chunks (%zu sequential-pair), %d threads, setup %.2f ms, convert %.2f ms, slot waits %.2f ms\n",
-                          nch, seq_chunks, c.pool->size(), ms_setup, t_conv, t_wait);
-    return true;
-}
-
-// Late loss H2D: a helper thread copies the losses chunk by chunk into a pinned ring and queues
-// each chunk's DMA on c.loss_stream behind the last endpoint/latency chunk (so the two never
-// share the PCIe link); loss_arrive() later joins it and orders the readers after the last DMA.
-void start_late_loss(srg_ctx& c, const srg_edge_list* g, DevGraph& dg, hipStream_t st, LateLoss& L, size_t a0 = 0,
-                     size_t a1 = ~(size_t)0) {
-    constexpr size_t CE = kCodecChunk;
-    constexpr int NB = kRingSlots;
-    ensure_rings(c);
-    L.ev_in = c.ev_lin;
-    L.ev_done = c.ev_ldone;
-    HIP_CHECK(hipEventRecord(c.ev_ledges, st));
-    HIP_CHECK(hipStreamWaitEvent(c.loss_stream, c.ev_ledges, 0));
-    dg.late = &L;
-    const int device = c.device;
-    L.th = std::thread([&c, g, &dg, &L, device, a0, a1]() {
-        constexpr size_t CE = (size_t)2 << 20;  // losses per chunk (8 MB)
-        constexpr int NB = 3;
-        try {
-            HIP_CHECK(hipSetDevice(device));
-            const bool dbg = srg_env::debug_overlap();
-            const auto t0 = std::chrono::steady_clock::now();
-            double t_copy = 0, t_wait = 0;
-            const size_t E = std::min<size_t>(g->num_edges, a1);  // this rank's slice [a0, E)
-            float* dloss = const_cast<float*>(dg.loss);
-            for (size_t ch = 0, e0 = a0; e0 < E; ++ch, e0 += CE) {
-                const int b = (int)(ch % NB);
-                auto ta = std::chrono::steady_clock::now();
-                if (ch >= (size_t)NB) HIP_CHECK(hipEventSynchronize(c.ev_lring[b]));
-                auto tb = std::chrono::steady_clock::now();
-                const size_t ne = std::min(CE, E - e0);
-                float* slot = (float*)c.h_lring + (size_t)b * CE;
-                c.pool->run([&](int w, int nw) {
-                    const size_t a = ne * w / nw, z = ne * (w + 1) / nw;
-                    std::memcpy(slot + a, g->packet_loss + e0 + a, (z - a) * 4);
-                });
-                t_wait += std::chrono::duration<double, std::milli>(tb - ta).count();
-                t_copy += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tb).count();
-                HIP_CHECK(hipMemcpyAsync(dloss + e0, slot, ne * 4, hipMemcpyHostToDevice, c.loss_stream));
-                HIP_CHECK(hipEventRecord(c.ev_lring[b], c.loss_stream));
-            }
-            HIP_CHECK(hipEventRecord(L.ev_in, c.loss_stream));
-            if (dbg) {
-                HIP_CHECK(hipEventSynchronize(L.ev_in));
-                std::fprintf(stderr, "late loss thread: %.2f ms to the last DMA, host copies %.2f ms, ring waits %.2f ms\n",
-                             std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(),
-                             t_copy, t_wait);
-            }
-        } catch (const Failure& f) {
-            L.err = f.msg;
-        } catch (const std::exception& e) {
-            L.err = e.what();
-        }
-    });
-}
+#include "h2d_codec.hip.h"
 
 int guard(char* errbuf, size_t errlen, const std::function<void()>& body) {
     try {
@@ -2941,436 +2624,7 @@ int guard(char* errbuf, size_t errlen, const std::function<void()>& body) {
     }
 }
 
-// out_key / out_diag (srg_internal_compute_table, RoutingInfo's key table): non-null = the latencies
-// leave as the build's u32 keys plus the diagonal's raw self-loop latencies; out_lat is unused then
-int host_entry(srg_ctx* c, const srg_edge_list* g, const uint32_t* nodes, uint32_t num_nodes, uint64_t* out_lat,
-               float* out_loss, srg_stats* stats, char* errbuf, size_t errlen, bool direct,
-               uint32_t* out_key = nullptr, uint64_t* out_diag = nullptr, srg_table* const* tabs = nullptr) {
-    const bool keys = out_key != nullptr;
-    if (keys && (direct || (c && c->comm && c->comm->nranks > 1) || (num_nodes && !out_diag))) {
-        set_err(errbuf, errlen, "key table: one rank, shortest paths only");
-        return SRG_ERR_ARG;
-    }
-    if (!c || !g || (num_nodes && (!nodes || !(out_lat || keys) || !out_loss)) ||
-        (g->num_edges && (!g->src || !g->dst || !g->latency_ns || !g->packet_loss))) {
-        set_err(errbuf, errlen, "null argument");
-        return SRG_ERR_ARG;
-    }
-    std::lock_guard<std::mutex> lk(c->mu);
-    // Page-lock the caller's output arrays on a helper thread, concurrently with the H2D copy
-    // and FW (≈10 ms for the 1.2 GB C3 table, measured), so finished rows can be DMA'd out
-    // asynchronously while later kernels run.  Small tables are copied at the end.
-    const size_t nn = (size_t)num_nodes * num_nodes;
-    struct Registration {
-        int device = 0;
-        std::thread th;
-        bool ok = false;
-        double ms = 0;
-        void* p[2] = {nullptr, nullptr};
-        void* view[2] = {nullptr, nullptr};  // device pointers of the mapped registrations
-        size_t b[2] = {0, 0};
-        hipStream_t wait = nullptr;
-        bool fault = true;
-        srg_table* tab[2] = {nullptr, nullptr};  // pooled tables (RoutingInfo): stay registered after the call
-        bool join() {
-            if (th.joinable()) th.join();
-            return ok;
-        }
-        void run() {
-            const auto t0 = std::chrono::steady_clock::now();
-            if (!b[0] || hipSetDevice(device) != hipSuccess) return;
-            for (int i = 0; i < 2; ++i) {
-                if (tab[i] && tab[i]->registered) {  // a recycled pooled table: nothing to do
-                    view[i] = tab[i]->view;
-                    continue;
-                }
-                advise_huge(p[i], b[i]);
-                if (fault) prefault(p[i], b[i], 8);
-                if (hipHostRegister(p[i], b[i], hipHostRegisterMapped) != hipSuccess) {
-                    if (i == 1 && !tab[0]) (void)hipHostUnregister(p[0]);
-                    return;
-                }
-                if (hipHostGetDevicePointer(&view[i], p[i], 0) != hipSuccess) view[i] = nullptr;
-                if (tab[i]) tab[i]->registered = true, tab[i]->view = view[i];
-            }
-            ms = ms_since(t0);
-            ok = true;
-        }
-        ~Registration() {
-            if (th.joinable()) th.join();
-            if (ok) {
-                (void)hipStreamSynchronize(wait);  // no copy into the buffers may be in flight
-                for (int i = 0; i < 2; ++i)
-                    if (!tab[i]) (void)hipHostUnregister(p[i]);
-            }
-        }
-    } reg;
-    reg.device = c->device;
-    reg.wait = c->d2h_stream;
-    reg.fault = srg_env::prefault_on();  // A/B
-    const bool early = !direct && nn * 12 >= ((size_t)64 << 20);
-    const bool ext = (bool)c->ext_reg;
-    // a rank of a group that fills only its own rows [n r / N, n (r+1) / N) of a table the ranks
-    // share (SRG_OPT_GATHER_OUTPUT 0, one process per GPU) page-locks only those rows: N processes
-    // pinning the whole shared table each cost N times the pinning, and a shared-memory table is
-    // typically 4-KB pages (~50 ms per 1.2 GB)
-    const bool rows_part = !direct && c->comm && c->comm->nranks > 1 && !c->gather_output;
-    const size_t reg_r0 = rows_part ? (size_t)num_nodes * c->comm->rank / c->comm->nranks : 0;
-    const size_t reg_r1 = rows_part ? (size_t)num_nodes * (c->comm->rank + 1) / c->comm->nranks : num_nodes;
-    const size_t lat_elem = keys ? 4 : 8;
-    unsigned char* out_lat_b = keys ? (unsigned char*)out_key : (unsigned char*)out_lat;  // the latency table
-    // pooled tables (srg_internal_compute_table): the whole mapping is registered once and kept
-    const bool pooled = early && !ext && !rows_part && tabs && tabs[0] && tabs[1] && tabs[0]->p == out_lat_b &&
-                        tabs[1]->p == (void*)out_loss && tabs[0]->cap >= nn * lat_elem && tabs[1]->cap >= nn * 4;
-    if (early && !ext) {
-        reg.p[0] = out_lat_b + reg_r0 * num_nodes * lat_elem;
-        reg.b[0] = (reg_r1 - reg_r0) * num_nodes * lat_elem;
-        reg.p[1] = out_loss + reg_r0 * num_nodes;
-        reg.b[1] = (reg_r1 - reg_r0) * num_nodes * 4;
-        if (pooled)
-            for (int i = 0; i < 2; ++i) reg.tab[i] = tabs[i], reg.b[i] = tabs[i]->cap;
-        reg.th = std::thread([&reg]() { reg.run(); });
-    }
-    return guard(errbuf, errlen, [&]() {
-        auto t0 = std::chrono::steady_clock::now();
-        if (stats) std::memset(stats, 0, sizeof(*stats));
-        HIP_CHECK(hipSetDevice(c->device));
-        hipStream_t st = c->stream;
-        const size_t E = g->num_edges, n = num_nodes;
-        DevGraph dg{g->num_vertices, (int)g->directed, g->num_edges, nullptr, nullptr, nullptr, nullptr,
-                    nullptr, g->node_ids};
-        // Multi-rank: every rank needs the whole edge list (W's rows feed the essential-entry
-        // records of every source), but each GPU has its own PCIe link and the GPUs a mesh of
-        // their own: rank r ships edges [E r/N, E (r+1)/N) and the slices are exchanged device to
-        // device.  The slice ranges are a function of (E, N) only, so every rank agrees on them.
-        const int nr = c->comm ? c->comm->nranks : 1, rk = c->comm ? c->comm->rank : 0;
-        const bool shard = nr > 1 && (c->edge_shard == 1 || (c->edge_shard < 0 && nr >= 4));
-        const size_t a0 = shard ? E * rk / nr : 0, a1 = shard ? E * (rk + 1) / nr : E;
-        // narrowed edge list over PCIe when it fits (falls back to the plain arrays otherwise)
-        // late loss: the losses follow the endpoints and latencies on their own stream, beside
-        // the W build and FW (dense u32 path: WL is built from them on c->loss_stream)
-        // (edge-sharded ranks ship their slices' losses late too; the slices are exchanged when
-        // the losses are first read, after FW -- loss_arrive)
-        const bool want_late = c->late_loss && !direct;
-        bool all_narrow = false, all_seq = false;
-        // FW beside the H2D (FwOverlap): one rank, undirected, the dense symmetric two-stream FW on
-        // 128-tiles, the codec with late losses; the chunks then cross on the comm stream (idle on
-        // one rank) while FW runs on the main stream
-        FwOverlap ov;
-        {
-            DevGraph probe{g->num_vertices, (int)g->directed, E};
-            const bool ov_want = c->fw_overlap && !direct && nr == 1 && want_late && c->h2d_codec && E >= ((size_t)1 << 20) &&
-                                 !g->directed && c->fw_symmetric && (c->fw_tile == 0 || c->fw_tile == 128) &&
-                                 g->num_vertices >= 256 && n > 0 && !choose_sparse(*c, probe);
-            if (ov_want) {
-                HIP_CHECK(hipStreamSynchronize(c->aux_stream));  // nothing of an aborted call still runs
-                ov.init(*c, g->num_vertices, std::vector<uint32_t>(nodes, nodes + n));
-            }
-        }
-        const hipStream_t hst = ov.on ? c->comm_stream : st;
-        ChunkFn on_chunk = nullptr;
-        if (ov.on) on_chunk = [&](size_t e0, size_t ne, const uint32_t* exc, size_t nexc, bool last) {
-            ov.chunk(dg, e0, ne, exc, nexc, last);
-        };
-        // (V > 65536: only a row-ordered list, through the sequential-pair chunks, can be narrowed;
-        // codec_in gives up on the first chunk that is neither)
-        const bool coded = c->h2d_codec && a1 - a0 >= ((size_t)1 << 20) &&
-                           codec_in(*c, g, dg, hst, a0, a1, !want_late, all_narrow, all_seq, on_chunk);
-        if (ov.on) ov.finish();  // the FW thread has enqueued every landed chunk's work
-        if (ov.on && !coded) ov.ok = false;
-        const int ov_early = ov.next;  // pivots enqueued while chunks were still crossing
-        if (stats && ov.on && ov.ok) stats->fw_overlap_pivots = ov_early;
-        if (ov.on && ov.ok && !ov.ended) ov.advance(ov.nb - 1);
-        if (ov.on && srg_env::debug_overlap()) {
-            std::fprintf(stderr, "fw-overlap: ok=%d pivots_during_h2d=%d of %d\n", ov.ok ? 1 : 0, ov_early, ov.nb);
-            if (ov.ok) ov.report();
-        }
-        // (started here, after the remaining pivots are enqueued -- an enqueue that holds this thread
-        // until FW nears its end -- the losses land ~3 ms after FW, but that wait overlaps GPU work:
-        // starting the thread before it measured 46.9-47.4 vs 46.5-46.6 ms, profiles/r06/late_loss/)
-        LateLoss late;
-        late.ls = c->loss_stream;
-        if (coded && want_late) start_late_loss(*c, g, dg, hst, late, a0, a1);
-        if (!coded) {
-            const size_t cnt = std::max<size_t>(E, 1);
-            dg.src = (uint32_t*)c->b_src.get(cnt * 4);
-            dg.dst = (uint32_t*)c->b_dst.get(cnt * 4);
-            dg.lat = (uint64_t*)c->b_lat.get(cnt * 8);
-            dg.loss = (float*)c->b_loss.get(cnt * 4);
-            if (a1 > a0) {
-                HIP_CHECK(hipMemcpyAsync((uint32_t*)dg.src + a0, g->src + a0, (a1 - a0) * 4, hipMemcpyHostToDevice, st));
-                HIP_CHECK(hipMemcpyAsync((uint32_t*)dg.dst + a0, g->dst + a0, (a1 - a0) * 4, hipMemcpyHostToDevice, st));
-                HIP_CHECK(hipMemcpyAsync((uint64_t*)dg.lat + a0, g->latency_ns + a0, (a1 - a0) * 8,
-                                         hipMemcpyHostToDevice, st));
-                HIP_CHECK(hipMemcpyAsync((float*)dg.loss + a0, g->packet_loss + a0, (a1 - a0) * 4,
-                                         hipMemcpyHostToDevice, st));
-            }
-        }
-        const bool sim = shard && std::strcmp(c->comm->kind(), "simulated") == 0;
-        if (sim && (c->sim_edges != g->src || c->sim_E != E)) {
-            // SRG_OPT_SIMULATE_RANK elides the exchange: the other slices are shipped once per
-            // edge list (a warm-up call), so later calls time this rank's slice and stay valid
-            auto put = [&](size_t e0, size_t e1) {
-                if (e1 <= e0) return;
-                HIP_CHECK(hipMemcpyAsync((uint32_t*)dg.src + e0, g->src + e0, (e1 - e0) * 4, hipMemcpyHostToDevice, st));
-                HIP_CHECK(hipMemcpyAsync((uint32_t*)dg.dst + e0, g->dst + e0, (e1 - e0) * 4, hipMemcpyHostToDevice, st));
-                HIP_CHECK(hipMemcpyAsync((uint64_t*)dg.lat + e0, g->latency_ns + e0, (e1 - e0) * 8,
-                                         hipMemcpyHostToDevice, st));
-                HIP_CHECK(hipMemcpyAsync((float*)dg.loss + e0, g->packet_loss + e0, (e1 - e0) * 4,
-                                         hipMemcpyHostToDevice, st));
-            };
-            put(0, a0);
-            put(a1, E);
-            c->sim_edges = g->src;
-            c->sim_E = E;
-        }
-        if (shard) {
-            std::vector<size_t> offs(nr), lens(nr);
-            auto gather = [&](const void* p, size_t elem) {
-                for (int q = 0; q < nr; ++q) {
-                    const size_t q0 = E * q / nr, q1 = E * (q + 1) / nr;
-                    offs[q] = q0 * elem;
-                    lens[q] = (q1 - q0) * elem;
-                }
-                c->comm->allgatherv(const_cast<void*>(p), offs.data(), lens.data(), st);
-            };
-            // the narrowest form every rank has: 0 = sequential-pair (each slice's u32 latencies +
-            // exceptions: 4 B per edge with the loss 8), 1 = u16 narrowing (8 B, 12 with the loss),
-            // 2 = plain (a rank shipped its slice plain: 20 B)
-            // forms 0 / 1: every rank is coded, so every rank ships its losses late -- exchanged when
-            // first read (loss_arrive); else now
-            auto late_or_gather_loss = [&]() {
-                if (dg.late) {
-                    dg.late->comm = c->comm;
-                    dg.late->offs.resize(nr);
-                    dg.late->lens.resize(nr);
-                    for (int q = 0; q < nr; ++q) {
-                        dg.late->offs[q] = E * q / nr * 4;
-                        dg.late->lens[q] = (E * (q + 1) / nr - E * q / nr) * 4;
-                    }
-                } else {
-                    gather(dg.loss, 4);
-                }
-            };
-            uint32_t* plain = (uint32_t*)c->b_red.get(16);
-            const uint32_t mine = !coded ? 2u : all_seq ? 0u : all_narrow ? 1u : 2u;
-            HIP_CHECK(hipMemcpyAsync(plain, &mine, 4, hipMemcpyHostToDevice, st));
-            c->comm->allreduce_max_u32(plain, 1, st);
-            uint32_t form = 2;
-            HIP_CHECK(hipMemcpyAsync(&form, plain, 4, hipMemcpyDeviceToHost, st));
-            HIP_CHECK(hipStreamSynchronize(st));
-            if (form == 0) {
-                // every slice's exception count, then every slice's exceptions (global index, src,
-                // dst), the u32 latencies and the losses; the other slices are decoded here
-                const size_t xbase = ((size_t)nr * 4 + 255) / 256 * 256;
-                uint32_t* xc = (uint32_t*)c->b_xexc.get(xbase);
-                const uint32_t my_n = (uint32_t)(c->slice_exc.size() / 3);
-                HIP_CHECK(hipMemcpyAsync(xc + rk, &my_n, 4, hipMemcpyHostToDevice, st));
-                for (int q = 0; q < nr; ++q) {
-                    offs[q] = (size_t)q * 4;
-                    lens[q] = 4;
-                }
-                c->comm->allgatherv(xc, offs.data(), lens.data(), st);
-                std::vector<uint32_t> cnt(nr);
-                HIP_CHECK(hipMemcpyAsync(cnt.data(), xc, (size_t)nr * 4, hipMemcpyDeviceToHost, st));
-                HIP_CHECK(hipStreamSynchronize(st));
-                if (sim)
-                    for (int q = 0; q < nr; ++q) cnt[q] = my_n;  // (a simulated rank hears nothing: its own size)
-                size_t tot = 0, mine_at = 0;
-                for (int q = 0; q < nr; ++q) {
-                    if (q == rk) mine_at = tot;
-                    offs[q] = xbase + tot * 12;
-                    lens[q] = (size_t)cnt[q] * 12;
-                    tot += cnt[q];
-                }
-                unsigned char* xb = (unsigned char*)c->b_xexc.get(xbase + std::max<size_t>(tot, 1) * 12);
-                if (my_n)
-                    HIP_CHECK(hipMemcpyAsync(xb + xbase + mine_at * 12, c->slice_exc.data(), (size_t)my_n * 12,
-                                             hipMemcpyHostToDevice, st));
-                c->comm->allgatherv(xb, offs.data(), lens.data(), st);
-                uint32_t* l32 = (uint32_t*)c->b_n32l.p;
-                gather(l32, 4);
-                late_or_gather_loss();
-                for (auto [e0, e1] : {std::pair<size_t, size_t>{0, a0}, std::pair<size_t, size_t>{a1, E}})
-                    if (e1 > e0 && !sim)
-                        k_decode_seq_global<<<grid_for(e1 - e0), kThreads, 0, st>>>(
-                            e0, e1, l32, (const uint32_t*)(xb + xbase), (uint32_t)tot, (uint32_t*)dg.src,
-                            (uint32_t*)dg.dst, (uint64_t*)dg.lat);
-                HIP_CHECK(hipGetLastError());
-            } else if (form == 1) {
-                uint16_t* s16 = (uint16_t*)c->b_n16s.p;
-                uint16_t* d16 = (uint16_t*)c->b_n16d.p;
-                uint32_t* l32 = (uint32_t*)c->b_n32l.p;
-                gather(s16, 2);
-                gather(d16, 2);
-                gather(l32, 4);
-                late_or_gather_loss();
-                // (a simulated rank received nothing: its other slices are the wide ones put once)
-                for (auto [e0, e1] : {std::pair<size_t, size_t>{0, a0}, std::pair<size_t, size_t>{a1, E}})
-                    if (e1 > e0 && !sim)
-                        k_widen_edges<<<grid_for(e1 - e0), kThreads, 0, st>>>(e1 - e0, s16 + e0, d16 + e0, l32 + e0,
-                                                                               (uint32_t*)dg.src + e0, (uint32_t*)dg.dst + e0,
-                                                                               (uint64_t*)dg.lat + e0);
-                HIP_CHECK(hipGetLastError());
-            } else {
-                gather(dg.src, 4);
-                gather(dg.dst, 4);
-                gather(dg.lat, 8);
-                if (dg.late) {  // (some rank shipped plain: no late exchange; this rank's losses first)
-                    dg.late->join();
-                    HIP_CHECK(hipStreamWaitEvent(st, dg.late->ev_in, 0));
-                }
-                gather(dg.loss, 4);
-            }
-        }
-        const uint32_t* dn = stage_in(c->b_nodes, nodes, n, hst);
-        if (hst != st) {  // the main stream's later work reads the landed edges and nodes
-            HIP_CHECK(hipEventRecord(c->ev_c, hst));
-            HIP_CHECK(hipStreamWaitEvent(st, c->ev_c, 0));
-        }
-        // multi-rank without the output exchange: the device holds only this rank's rows [p0, p1)
-        // (the plan's split, make_plan / run_sparse); dol / dos then point p0 rows before that
-        // allocation, so the kernels' absolute row indices land in it (C4 at 8 ranks: 3.75 GB per
-        // GPU instead of 30 GB)
-        const bool own_rows_only = !direct && c->comm && c->comm->nranks > 1 && !c->gather_output;
-        const size_t q0 = own_rows_only ? (uint64_t)n * c->comm->rank / c->comm->nranks : 0;
-        const size_t q1 = own_rows_only ? (uint64_t)n * (c->comm->rank + 1) / c->comm->nranks : n;
-        const size_t dev_nn = (q1 - q0) * n;
-        uint64_t* dol = reinterpret_cast<uint64_t*>(reinterpret_cast<uintptr_t>(c->b_olat.get(std::max<size_t>(dev_nn, 1) * 8)) -
-                                                    q0 * n * 8);
-        float* dos = reinterpret_cast<float*>(reinterpret_cast<uintptr_t>(c->b_oloss.get(std::max<size_t>(dev_nn, 1) * 4)) -
-                                              q0 * n * 4);
-        HIP_CHECK(hipStreamSynchronize(hst));  // (beside FW when it started early: st still runs it)
-        const double ms_h2d = ms_since(t0);
-        // u64 output of a dense u32 build on one rank: the latency rows cross PCIe as the build's u32
-        // keys and are widened on the host (HostSink::send_keys; 0.6 GB less D2H at C3); a build that
-        // turns out to need u64 keys ships the u64 rows instead (run_dense clears sink.widen)
-        bool ikeys = !keys && !direct && early && nr == 1 && c->sdma.ok && c->d2h_mode == 1 && c->h_ring &&
-                     c->pool && (size_t)n * 4 <= c->h_ring_bytes / 3 && !srg_env::no_key_d2h();
-        {
-            DevGraph probe{g->num_vertices, (int)g->directed, E};
-            ikeys = ikeys && !choose_sparse(*c, probe);
-        }
-        bool kmode = keys || ikeys;
-        // key mode: the device key table in the latency buffer's room, the diagonal beside it; the
-        // kernels see them through the context for this call
-        uint32_t* dkey = kmode ? reinterpret_cast<uint32_t*>(dol) : nullptr;
-        uint64_t* ddiag = kmode ? (uint64_t*)c->b_odiag.get(std::max<size_t>(n, 1) * 8) : nullptr;
-        struct KeyScope {
-            srg_ctx* c;
-            ~KeyScope() { c->kout_key = nullptr, c->kout_diag = nullptr; }
-        } key_scope{c};
-        c->kout_key = dkey;
-        c->kout_diag = ddiag;
-        HostSink sink;
-        sink.lat = keys ? reinterpret_cast<uint64_t*>(out_key) : out_lat;  // (a host table pointer either way)
-        sink.widen = ikeys;
-        sink.pool = c->pool;
-        sink.ring = (unsigned char*)c->h_ring;
-        sink.ring_slot = c->h_ring_bytes / 3;
-        sink.loss = out_loss;
-        sink.n = n;
-        sink.cs = c->d2h_stream;
-        sink.ev = c->ev_e;
-        if (early) {
-            sink.mode = c->d2h_mode;
-            sink.sdma = &c->sdma;
-            sink.device = c->device;
-            if (ext) {
-                sink.ready = [c, &reg, &sink]() {
-                    void* v[2] = {nullptr, nullptr};
-                    if (!c->ext_reg(v, &reg.ms)) return false;
-                    sink.lat_view = v[0];
-                    sink.loss_view = v[1];
-                    return true;
-                };
-            } else {
-                sink.ready = [&reg, &sink, reg_r0, num_nodes]() {
-                    if (!reg.join()) return false;
-                    // views of rows [reg_r0, ...): based so that row r lands at view + r * n
-                    sink.lat_view = (unsigned char*)reg.view[0] - reg_r0 * num_nodes * 8;
-                    sink.loss_view = (unsigned char*)reg.view[1] - reg_r0 * num_nodes * 4;
-                    return true;
-                };
-            }
-        }
-        c->own_row0 = 0;
-        c->own_row1 = ~(size_t)0;
-        if (direct) {
-            direct_device(*c, dg, dn, num_nodes, dol, dos, st);
-        } else {
-            compute_device(*c, dg, dn, num_nodes, dol, dos, st, stats, early ? &sink : nullptr, ov.on ? &ov : nullptr);
-            if (ikeys && !sink.widen) {  // the build took u64 keys (run_dense dropped the key table)
-                ikeys = false;
-                kmode = keys;
-                dkey = nullptr;
-                ddiag = nullptr;
-            }
-        }
-        if (dg.late) {  // a path that never read the losses (error-free early return): drain
-            dg.late->join();
-            HIP_CHECK(hipStreamSynchronize(c->loss_stream));
-        }
-        // multi-rank without the output exchange: only this rank's rows [own_row0, own_row1) leave
-        // the device (possibly none), and min_latency_ns is over those rows only
-        const bool rows_only = c->comm && c->comm->nranks > 1 && !c->gather_output && !direct;
-        const size_t r0 = rows_only ? std::min<size_t>(c->own_row0, n) : 0;
-        const size_t r1 = rows_only ? std::min<size_t>(c->own_row1, n) : n;
-        const size_t rows_off = r0 * n, rows_nn = r1 > r0 ? (r1 - r0) * n : 0;
-        auto t1 = std::chrono::steady_clock::now();
-        unsigned long long hmin = ~0ull;
-        if (rows_nn && stats) {  // smallest latency over the table (feeds the runahead, manager.rs:238-243)
-            unsigned long long* dmin = (unsigned long long*)c->b_multi.get(16);
-            HIP_CHECK(hipMemsetAsync(dmin, 0xFF, 16, st));
-            if (kmode) {  // smallest key (x unit below) and smallest diagonal latency
-                k_min_u32<<<grid_for(rows_nn, 1024), kThreads, 0, st>>>(dkey + rows_off, rows_nn, dmin);
-                k_min_u64<<<grid_for(n, 1024), kThreads, 0, st>>>(ddiag, n, dmin + 1);
-            } else {
-                k_min_u64<<<grid_for(rows_nn, 1024), kThreads, 0, st>>>(dol + rows_off, rows_nn, dmin);
-            }
-            HIP_CHECK(hipMemcpyAsync(c->hbox + 64 * MS_MIN, dmin, 16, hipMemcpyDeviceToHost, st));
-        }
-        if (rows_nn && !sink.lat_sent) {
-            if (keys)
-                HIP_CHECK(hipMemcpyAsync(out_key + rows_off, dkey + rows_off, rows_nn * 4, hipMemcpyDeviceToHost, st));
-            else if (!ikeys)
-                HIP_CHECK(hipMemcpyAsync(out_lat + rows_off, dol + rows_off, rows_nn * 8, hipMemcpyDeviceToHost, st));
-        }
-        if (keys && n) HIP_CHECK(hipMemcpyAsync(out_diag, ddiag, n * 8, hipMemcpyDeviceToHost, st));
-        std::vector<uint64_t> hdiag(ikeys ? n : 0);  // the diagonal the widened rows are patched with
-        if (ikeys && n) HIP_CHECK(hipMemcpyAsync(hdiag.data(), ddiag, n * 8, hipMemcpyDeviceToHost, st));
-        if (rows_nn && !sink.loss_sent)
-            HIP_CHECK(hipMemcpyAsync(out_loss + rows_off, dos + rows_off, rows_nn * 4, hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipStreamSynchronize(st));
-        if (rows_nn && stats) {
-            hmin = rb_get<unsigned long long>(*c, MS_MIN);
-            if (kmode) {
-                const unsigned long long dmin = *reinterpret_cast<const unsigned long long*>(c->hbox + 64 * MS_MIN + 8);
-                const uint64_t unit = stats->latency_unit_ns ? stats->latency_unit_ns : 1;
-                hmin = std::min<unsigned long long>(hmin == ~0ull ? ~0ull : hmin * unit, dmin);
-            }
-        }
-        if (ikeys && rows_nn && !sink.lat_sent) {
-            // the rows were not shipped early (the caller's tables could not be page-locked): keys now
-            sink.send_keys(st, dkey, r0, r1 - r0, sink.key_unit);
-            sink.lat_sent = true;
-        }
-        sink.finish();
-        if (ikeys)
-            for (size_t r = r0; r < r1; ++r) out_lat[r * n + r] = hdiag[r];  // raw self-loop weights (mod.rs:211-217)
-        if (stats) {
-            stats->ms_h2d = ms_h2d;
-            stats->ms_d2h = ms_since(t1);  // the D2H not hidden behind kernels
-            stats->ms_total = ms_since(t0);
-            stats->ms_host_register = ext ? (sink.registered ? reg.ms : -1.0) : reg.join() ? reg.ms : -1.0;
-            stats->d2h_overlapped_bytes = sink.early_bytes;
-            stats->d2h_key_rows = ikeys ? 1 : 0;
-            stats->ms_key_widen = sink.ms_widen;
-            stats->min_latency_ns = hmin;
-            if (direct) stats->path_kind = SRG_PATH_DIRECT;
-        }
-    });
-}
+#include "host_entry.hip.h"
 }  // namespace
 
 extern "C" {

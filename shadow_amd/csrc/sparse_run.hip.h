@@ -54,9 +54,8 @@ bool run_sparse(srg_ctx& c, const DevGraph& g, const uint32_t* nodes, uint32_t n
     }
     // this rank's sources, in graph-locality (BFS) order, in batches of 64 lanes: sources of
     // one batch are close to each other, so their Bellman-Ford frontiers move together
-    const uint32_t p0 = (uint32_t)((uint64_t)rk * n / G), p1 = (uint32_t)((uint64_t)(rk + 1) * n / G);
-    c.own_row0 = p0;  // this rank's rows: positions [p0, p1) of `nodes`
-    c.own_row1 = p1;
+    const Range own = rank_rows(n, rk, G);  // this rank's rows: positions [p0, p1) of `nodes`
+    const uint32_t p0 = (uint32_t)own.lo, p1 = (uint32_t)own.hi;
     const uint32_t nloc = p1 - p0;
     const uint32_t nbatch = (nloc + 63) / 64;
     const int dbg = srg_env::debug_sparse();  // (read once per build)
@@ -277,13 +276,9 @@ bool run_sparse(srg_ctx& c, const DevGraph& g, const uint32_t* nodes, uint32_t n
     }
     double ms_exchange = 0;
     if (multi && c.gather_output) {
-        std::vector<size_t> offs(G), lens(G);
+        std::vector<size_t> offs, lens;
         for (int elem : {8, 4}) {
-            for (int r = 0; r < G; ++r) {
-                const size_t a0 = (uint64_t)r * n / G, a1 = (uint64_t)(r + 1) * n / G;
-                offs[r] = a0 * n * elem;
-                lens[r] = (a1 - a0) * n * elem;
-            }
+            slice_tables(n, G, (size_t)n * elem, offs, lens);
             c.comm->allgatherv(elem == 8 ? (void*)out_lat : (void*)out_loss, offs.data(), lens.data(), st);
         }
         ms_exchange = tm.lap();

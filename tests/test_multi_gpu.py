@@ -170,17 +170,27 @@ def test_edge_sharded_host_entry(G, shard):
         assert bits_equal(t.packet_loss, loss), f"rank {r} loss"
 
 
-@pytest.mark.parametrize("G,V,order", [(2, 2100, "rows"), (4, 3000, "rows"), (2, 2100, "shuffled")])
+@pytest.mark.parametrize("G,V,order", [(2, 2100, "rows"), (4, 3000, "rows"), (2, 2100, "shuffled"),
+                                       (2, 2100, "rows_one_plain")])
 def test_edge_sharded_codec_slices(G, V, order):
     """Edge sharding with the H2D codec active on every rank's slice (>= 2^20 edges per slice): a
     row-ordered list crosses and is exchanged in the sequential-pair form (u32 latencies + row-start
     exceptions, decoded on every rank), a shuffled one in the u16 narrowing; both equal the
-    single-GPU build."""
+    single-GPU build.  rows_one_plain: a latency of 2^32 in the last rank's slice, so that rank's
+    codec gives up and ships plain; the exchange then takes the plain form on every rank, and the
+    ranks that stayed coded and started their losses late join that thread before gathering."""
     e = synth.atlas_like(V, seed=V)
     if order == "shuffled":
         from shadow_amd.graph import Edges
         p = np.random.default_rng(V).permutation(e.num_edges)
         e = Edges(V, e.src[p], e.dst[p], e.latency_ns[p], e.packet_loss[p], False)
+    if order == "rows_one_plain":
+        from shadow_amd.graph import Edges
+        lat = e.latency_ns.copy()
+        k = e.num_edges * (G - 1) // G + 5  # in the last rank's slice [E (G-1) / G, E)
+        assert e.src[k] != e.dst[k]
+        lat[k] = 2 ** 32
+        e = Edges(V, e.src, e.dst, lat, e.packet_loss, False)
     assert e.num_edges >= G * (1 << 20) + 2
     nodes = list(range(0, V, 7))
     r1 = Router(0)
