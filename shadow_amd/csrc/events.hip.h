@@ -116,46 +116,15 @@ __device__ __forceinline__ void ev_block_reduce(unsigned long long tmin, unsigne
     }
 }
 
-__global__ void __launch_bounds__(256) k_ev_prep(EvIn in, uint64_t* __restrict__ deliver, EvReduce* red) {
-    unsigned long long tmin = ~0ull, tmax = 0, imin = ~0ull, imax = 0, lmin = ~0ull;
-    uint32_t dmax = 0, smax = 0, bad = 0;
-    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < in.n; i += (size_t)gridDim.x * blockDim.x) {
-        const uint32_t a = in.src_node[i], b = in.dst_node[i], dh = in.dst_host[i], sh = in.src_host[i];
-        if (a >= in.tn || b >= in.tn) {
-            bad |= 2;
-            continue;
-        }
-        if (dh >= in.num_hosts) {
-            bad |= 1;
-            continue;
-        }
-        const uint64_t delay = in.table[(size_t)a * in.tn + b];
-        const uint64_t s = in.send_ns[i];
-        if (s > ~0ull - delay) {
-            bad |= 4;
-            continue;
-        }
-        uint64_t t = s + delay;
-        t = t < in.round_end ? in.round_end : t;
-        deliver[i] = t;
-        const uint64_t id = in.event_id[i];
-        tmin = t < tmin ? t : tmin;
-        tmax = t > tmax ? t : tmax;
-        imin = id < imin ? id : imin;
-        imax = id > imax ? id : imax;
-        lmin = delay < lmin ? delay : lmin;
-        dmax = dh > dmax ? dh : dmax;
-        smax = sh > smax ? sh : smax;
-    }
-    ev_block_reduce(tmin, tmax, imin, imax, lmin, dmax, smax, bad, red);
-}
-
-// ---- the whole of send_packet (srg_send_packets_device) -------------------------------------
-// The prep pass with the drop decision in front (send_rule.h) and either table form behind it.
-// A dropped event gets status 0 and deliver = UINT64_MAX and feeds no reduction: the reference
-// returns before the latency lookup (worker.rs:381-389), so it can neither overflow send + delay
-// nor widen a key field nor lower a minimum.  The key pass parks it behind host `num_hosts`
-// (k_ev_keys<.., true>) and the finish pass leaves the parked run out of the equal-key check.
+// ---- the prep pass, for both batch calls -----------------------------------------------------
+// SEND = false (srg_order_packet_events_device): the latency is in.table[a * tn + b], every event is
+// sent; sx and status are not used.
+// SEND = true, the whole of send_packet (srg_send_packets_device): the drop decision in front
+// (send_rule.h) and either table form behind it.  A dropped event gets status 0 and
+// deliver = UINT64_MAX and feeds no reduction: the reference returns before the latency lookup
+// (worker.rs:381-389), so it can neither overflow send + delay nor widen a key field nor lower a
+// minimum.  The key pass parks it behind host `num_hosts` (k_ev_keys<.., true>) and the finish pass
+// leaves the parked run out of the equal-key check.
 struct EvSendIn {
     PathLatency tab;
     const float* loss;  // [tn x tn], null: every packet is sent
@@ -166,11 +135,12 @@ struct EvSendIn {
 
 struct EvSendReduce {
     EvReduce r;
-    unsigned long long sent;
+    unsigned long long sent;  // SEND only
 };
 
-__global__ void __launch_bounds__(256) k_ev_send_prep(EvIn in, EvSendIn sx, uint8_t* __restrict__ status,
-                                                      uint64_t* __restrict__ deliver, EvSendReduce* red) {
+template <bool SEND>
+__global__ void __launch_bounds__(256) k_ev_prep(EvIn in, EvSendIn sx, uint8_t* __restrict__ status,
+                                                 uint64_t* __restrict__ deliver, EvSendReduce* red) {
     unsigned long long tmin = ~0ull, tmax = 0, imin = ~0ull, imax = 0, lmin = ~0ull;
     uint32_t dmax = 0, smax = 0, bad = 0, sent = 0;
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < in.n; i += (size_t)gridDim.x * blockDim.x) {
@@ -183,15 +153,21 @@ __global__ void __launch_bounds__(256) k_ev_send_prep(EvIn in, EvSendIn sx, uint
             bad |= 1;
             continue;
         }
-        const uint64_t s = in.send_ns[i];
-        // both table gathers are issued before the decision (each misses to HBM: one behind the other
-        // costs the pass a second round trip per event); a dropped event's latency is not used
-        const float loss = sx.loss ? sx.loss[(size_t)a * in.tn + b] : 0.0f;
-        const uint64_t delay = path_latency(sx.tab, a, b);
-        if (sx.loss && dropped(loss, sx.chance[i], sx.payload[i], s, sx.bootstrap_end)) {
-            status[i] = 0;
-            deliver[i] = ~0ull;
-            continue;
+        uint64_t delay, s;
+        if constexpr (SEND) {
+            s = in.send_ns[i];
+            // both table gathers are issued before the decision (each misses to HBM: one behind the other
+            // costs the pass a second round trip per event); a dropped event's latency is not used
+            const float loss = sx.loss ? sx.loss[(size_t)a * in.tn + b] : 0.0f;
+            delay = path_latency(sx.tab, a, b);
+            if (sx.loss && dropped(loss, sx.chance[i], sx.payload[i], s, sx.bootstrap_end)) {
+                status[i] = 0;
+                deliver[i] = ~0ull;
+                continue;
+            }
+        } else {
+            delay = in.table[(size_t)a * in.tn + b];
+            s = in.send_ns[i];
         }
         if (s > ~0ull - delay) {
             bad |= 4;
@@ -199,9 +175,11 @@ __global__ void __launch_bounds__(256) k_ev_send_prep(EvIn in, EvSendIn sx, uint
         }
         uint64_t t = s + delay;
         t = t < in.round_end ? in.round_end : t;
-        status[i] = 1;
+        if constexpr (SEND) {
+            status[i] = 1;
+            ++sent;
+        }
         deliver[i] = t;
-        ++sent;
         const uint64_t id = in.event_id[i];
         tmin = t < tmin ? t : tmin;
         tmax = t > tmax ? t : tmax;
@@ -211,8 +189,10 @@ __global__ void __launch_bounds__(256) k_ev_send_prep(EvIn in, EvSendIn sx, uint
         dmax = dh > dmax ? dh : dmax;
         smax = sh > smax ? sh : smax;
     }
-    for (int off = 32; off; off >>= 1) sent += __shfl_xor(sent, off, 64);
-    if ((threadIdx.x & 63) == 0 && sent) atomicAdd(&red->sent, (unsigned long long)sent);
+    if constexpr (SEND) {
+        for (int off = 32; off; off >>= 1) sent += __shfl_xor(sent, off, 64);
+        if ((threadIdx.x & 63) == 0 && sent) atomicAdd(&red->sent, (unsigned long long)sent);
+    }
     ev_block_reduce(tmin, tmax, imin, imax, lmin, dmax, smax, bad, &red->r);
 }
 

@@ -1,14 +1,16 @@
 // route_trees.hip.h -- the route tree of whole source rows, and link loads pushed up those trees
 // (srg_route_trees_device, srg_link_loads_trees_device).  A section of routing.hip's translation
-// unit, included there after routes.hip.h (it uses RouteIn, RouteState, rt_run_add, rt_sat_add,
-// route_check_table and route_fail_pass0 from it); not a header to include elsewhere.
+// unit, included there after routes.hip.h; not a header to include elsewhere.  From routes.hip.h it
+// takes the in-edge list builder with its essential filter (route_prepare(essential), k_rt_csc<.,
+// true>, the lists' workspace b_rt_*), RouteIn, RouteState (below_q is set only here),
+// route_read_state, rt_sat_add, route_check_table and route_fail_pass0.
 //
 // For one source s the routes of route_rule.h to all targets form a tree: the tie rule makes every
 // route unique, and the route to t through u ends with the route to u.  So one predecessor per
 // (s, t) is the whole answer, where routes.hip.h walks every pair back to s on its own.
 //
-//   1. Essential in-edge lists (k_rtt_csc): the CSC of routes.hip.h, but an arc u -> t is kept only
-//      when lat(e) == D[u][t].  A route edge (u, t) is itself a shortest path u -> t: a match has
+//   1. Essential in-edge lists (k_rt_csc<., true>): the CSC of routes.hip.h, but an arc u -> t is kept
+//      only when lat(e) == D[u][t].  A route edge (u, t) is itself a shortest path u -> t: a match has
 //      D[s][u] + lat == D[s][t] <= D[s][u] + D[u][t], so lat <= D[u][t], and D[u][t] <= lat because
 //      the edge is a path.  On a shortest-path table the filter therefore removes no candidate of
 //      any row, and the tie rule's minimum is unchanged.  The filter reads the entries (u, t) of
@@ -26,85 +28,13 @@
 //      is done.  A chain has V - 1 levels of V entries each: correct, and slow.
 //
 // Rows are processed in batches sized by a workspace budget (kRttBudget) or SRG_OPT_ROUTE_TREE_ROWS.
-// The workspace is the context's (b_rtt_*), freed by srg_destroy.
+// The workspace is the context's: the lists in b_rt_* (every call rebuilds them under the context's
+// lock, so the pairwise calls and these share one set), the trees' own buffers in b_rtt_*; freed by
+// srg_destroy.
 
 constexpr size_t kRttBudget = (size_t)4 << 30;  // workspace bytes a batch of rows may take
 constexpr uint32_t kRttLdsJumpV = 4096;          // doubling: 16 * V bytes of LDS up to this V
 constexpr uint32_t kRttLdsSubV = 8192;           // push: 8 * V bytes of LDS up to this V
-
-struct RttState {
-    unsigned long long bad_q;     // smallest unexplained entry (trees: row * n + t; loads: s * n + t); ~0 = none
-    unsigned long long noedge_q;  // loads: smallest diagonal pair with a count and no self-loop; ~0 = none
-    unsigned long long below_q;   // smallest u * n + t of an arc with lat(e) < D[u][t]; ~0 = none
-    unsigned long long total;     // sum of hops
-    uint32_t max_hops;
-    uint32_t bad_arg;             // a source >= n
-    uint32_t bad_edge;            // bit 0: an endpoint >= V; bit 1: a non-self-loop edge of latency 0
-    uint32_t pad;
-};
-
-// k_rt_csc with the essential filter.  FILL = false: counts, self-loops, the edge checks and the
-// below-entry flag; FILL = true: the arcs take their slots (same predicate, so the same counts).
-template <bool FILL>
-__global__ void __launch_bounds__(256) k_rtt_csc(uint64_t E, const uint32_t* __restrict__ src,
-                                                 const uint32_t* __restrict__ dst, const uint64_t* __restrict__ lat,
-                                                 const float* __restrict__ loss, int directed, uint32_t V,
-                                                 PathLatency tab, int filter, uint32_t* __restrict__ ctr,
-                                                 uint32_t* __restrict__ ce, uint32_t* __restrict__ cu,
-                                                 uint64_t* __restrict__ cl, float* __restrict__ cp,
-                                                 uint32_t* __restrict__ selfedge, RttState* st) {
-    const uint32_t lane = threadIdx.x & 63;
-    const size_t stride = (size_t)gridDim.x * blockDim.x;
-    uint32_t bad = 0;
-    unsigned long long below = ~0ull;
-    // whole waves stay in the loop together (rt_run_add needs every lane)
-    for (size_t e0 = blockIdx.x * (size_t)blockDim.x + (threadIdx.x & ~63u); e0 < E; e0 += stride) {
-        const size_t e = e0 + lane;
-        const bool in = e < E;
-        const uint32_t s = in ? src[e] : 0u, t = in ? dst[e] : 0u;
-        const bool ok = in && s < V && t < V;
-        const bool arc = ok && s != t;
-        const uint64_t w = arc ? lat[e] : 0;
-        const float pl = FILL && arc ? loss[e] : 0.0f;
-        if (!FILL) {
-            if (in && !ok) bad |= 1u;
-            if (arc && w == 0) bad |= 2u;
-            if (ok && s == t) atomicMin(&selfedge[s], (uint32_t)e);
-        }
-        bool keep = arc;
-        if (filter && arc) {
-            const uint64_t d = path_latency(tab, s, t);
-            keep = w == d;
-            if (!FILL && w < d) below = min(below, (unsigned long long)s * V + t);
-        }
-        uint32_t p = rt_run_add(ctr, t, keep);
-        if (FILL && keep) {
-            ce[p] = (uint32_t)e;
-            cu[p] = s;
-            cl[p] = w;
-            cp[p] = pl;
-        }
-        if (!directed) {
-            keep = arc;
-            if (filter && arc) {
-                const uint64_t d = path_latency(tab, t, s);
-                keep = w == d;
-                if (!FILL && w < d) below = min(below, (unsigned long long)t * V + s);
-            }
-            p = rt_run_add(ctr, s, keep);
-            if (FILL && keep) {
-                ce[p] = (uint32_t)e;
-                cu[p] = t;
-                cl[p] = w;
-                cp[p] = pl;
-            }
-        }
-    }
-    if (!FILL) {
-        if (bad) atomicOr(&st->bad_edge, bad);
-        if (below != ~0ull) atomicMin(&st->below_q, below);
-    }
-}
 
 // The predecessor of every (row, t) of a batch.  G lanes per target; pe / pv are the batch's rows
 // ([rows * V], pv may be null).  The source's column and an unexplained entry get ROUTE_TREE_NONE;
@@ -112,7 +42,7 @@ __global__ void __launch_bounds__(256) k_rtt_csc(uint64_t E, const uint32_t* __r
 template <int G>
 __global__ void __launch_bounds__(256) k_rtt_pred(RouteIn in, const uint32_t* __restrict__ sources, uint32_t row0,
                                                   uint32_t rows, uint32_t* __restrict__ pe, uint32_t* __restrict__ pv,
-                                                  int flag_bad, RttState* st) {
+                                                  int flag_bad, RouteState* st) {
     constexpr uint32_t TPB = 256 / G;  // targets per workgroup step
     const uint32_t V = in.V;
     const uint32_t gl = threadIdx.x & (G - 1), grp = threadIdx.x / G;
@@ -174,7 +104,7 @@ __global__ void __launch_bounds__(256) k_rtt_double(uint32_t V, const uint32_t* 
                                                     uint32_t* __restrict__ hops, uint32_t* __restrict__ first,
                                                     const unsigned long long* __restrict__ counts,
                                                     const uint32_t* __restrict__ selfedge, uint32_t* __restrict__ rowmax,
-                                                    RttState* st) {
+                                                    RouteState* st) {
     const uint32_t row = blockIdx.x;
     const uint32_t s = sources ? sources[row0 + row] : row0 + row;
     if (s >= V) return;  // (k_rtt_pred flagged it; workgroup-uniform)
@@ -298,60 +228,6 @@ __global__ void __launch_bounds__(256) k_rtt_push(uint32_t V, const uint32_t* __
 }
 
 // ---- host side --------------------------------------------------------------------------------
-// The edge checks and the (essential, when filter) in-edge lists of this call's graph (V >= 1).
-// Synchronises once; *s0 is the state after the counting pass (bad_edge, below_q).
-RouteIn rtt_prepare(srg_ctx& c, const srg_edge_list* g, const srg_path_table_dev* t, int filter, hipStream_t st,
-                    RttState** state_dev, RttState* s0, uint32_t* num_arcs) {
-    const uint32_t V = g->num_vertices;
-    const uint64_t E = g->num_edges;
-    const PathLatency tab{t->latency_ns, t->latency_key, t->diag_ns, t->unit_ns, t->n};
-    uint32_t* off = (uint32_t*)c.b_rtt_off.get(((size_t)V + 1) * 4);
-    uint32_t* cur = (uint32_t*)c.b_rtt_cur.get(((size_t)V + 1) * 4);
-    uint32_t* self = (uint32_t*)c.b_rtt_self.get((size_t)V * 4);
-    RttState* sd = (RttState*)c.b_rtt_state.get(sizeof(RttState));
-    const RttState init{~0ull, ~0ull, ~0ull, 0ull, 0u, 0u, 0u, 0u};
-    HIP_CHECK(hipMemcpyAsync(sd, &init, sizeof(RttState), hipMemcpyHostToDevice, st));
-    HIP_CHECK(hipMemsetAsync(cur, 0, ((size_t)V + 1) * 4, st));
-    HIP_CHECK(hipMemsetAsync(self, 0xFF, (size_t)V * 4, st));
-    if (E)
-        k_rtt_csc<false><<<grid_for(E, 2048), kThreads, 0, st>>>(E, g->src, g->dst, g->latency_ns, g->packet_loss,
-                                                                (int)g->directed, V, tab, filter, cur, nullptr, nullptr,
-                                                                nullptr, nullptr, self, sd);
-    HIP_CHECK(hipGetLastError());
-    size_t tb = 0;
-    HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, cur, off, (int)(V + 1), st));
-    void* tmp = c.b_rtt_tmp.get(tb);
-    HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(tmp, tb, cur, off, (int)(V + 1), st));
-    uint32_t arcs = 0;
-    HIP_CHECK(hipMemcpyAsync(s0, sd, sizeof(RttState), hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipMemcpyAsync(&arcs, off + V, 4, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    if (s0->bad_edge & 1) fail(SRG_ERR_ARG, "edge endpoint out of range (>= num_vertices)");
-    if (s0->bad_edge & 2)
-        fail(SRG_ERR_ARG, "an edge between two vertices has latency 0 (the walk's termination rests on latencies >= 1)");
-    uint32_t* ce = (uint32_t*)c.b_rtt_ce.get((size_t)arcs * 4);
-    uint32_t* cu = (uint32_t*)c.b_rtt_cu.get((size_t)arcs * 4);
-    uint64_t* cl = (uint64_t*)c.b_rtt_cl.get((size_t)arcs * 8);
-    float* cp = (float*)c.b_rtt_cp.get((size_t)arcs * 4);
-    if (arcs) {
-        HIP_CHECK(hipMemcpyAsync(cur, off, ((size_t)V + 1) * 4, hipMemcpyDeviceToDevice, st));
-        k_rtt_csc<true><<<grid_for(E, 2048), kThreads, 0, st>>>(E, g->src, g->dst, g->latency_ns, g->packet_loss,
-                                                               (int)g->directed, V, tab, filter, cur, ce, cu, cl, cp, self,
-                                                               sd);
-        HIP_CHECK(hipGetLastError());
-    }
-    *state_dev = sd;
-    *num_arcs = arcs;
-    return RouteIn{off, ce, cu, cl, cp, self, tab, t->packet_loss, V};
-}
-
-RttState rtt_read_state(RttState* sd, hipStream_t st) {
-    RttState s;
-    HIP_CHECK(hipMemcpyAsync(&s, sd, sizeof(RttState), hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    return s;
-}
-
 // rows per batch: the option, or what the budget allows of rows that take `row_bytes` each
 uint32_t rtt_batch_rows(const srg_ctx& c, uint32_t rows, size_t row_bytes) {
     uint64_t r = c.route_tree_rows > 0 ? (uint64_t)c.route_tree_rows : kRttBudget / std::max<size_t>(row_bytes, 1);
@@ -362,7 +238,7 @@ uint32_t rtt_batch_rows(const srg_ctx& c, uint32_t rows, size_t row_bytes) {
 // G: a wave per target where the essential lists average a wave's width or more (V targets, off[V]
 // arcs), 16 lanes per target below that; SRG_ROUTE_TREE_GROUP forces either.
 void rtt_launch_pred(const RouteIn& in, uint32_t arcs, const uint32_t* sources, uint32_t row0, uint32_t rows,
-                     uint32_t* pe, uint32_t* pv, int flag_bad, RttState* sd, hipStream_t st) {
+                     uint32_t* pe, uint32_t* pv, int flag_bad, RouteState* sd, hipStream_t st) {
     const uint32_t V = in.V;
     const int forced = srg_env::route_tree_group();
     const bool wave = forced ? forced == 64 : arcs / V >= 64;
@@ -380,7 +256,7 @@ void rtt_launch_pred(const RouteIn& in, uint32_t arcs, const uint32_t* sources, 
 
 void rtt_launch_double(bool lds, uint32_t V, const uint32_t* sources, uint32_t row0, uint32_t rows, const uint32_t* pe,
                        const uint32_t* pv, unsigned long long* scratch, uint32_t* hops, uint32_t* first,
-                       const unsigned long long* counts, const uint32_t* self, uint32_t* rowmax, RttState* sd,
+                       const unsigned long long* counts, const uint32_t* self, uint32_t* rowmax, RouteState* sd,
                        hipStream_t st) {
     if (lds)
         k_rtt_double<true><<<rows, kThreads, (size_t)V * 16, st>>>(V, sources, row0, pe, pv, nullptr, hops, first, counts,
@@ -401,15 +277,16 @@ void route_trees_device(srg_ctx& c, const srg_edge_list* g, const srg_path_table
     if (!out_pe) fail(SRG_ERR_ARG, "null argument");
     if (V == 0 || (!sources && ns > V)) fail(SRG_ERR_ARG, "source index out of range (>= n)");
     if (res) res->num_pairs = (uint64_t)ns * (V - 1);
-    RttState* sd = nullptr;
-    RttState s0;
-    uint32_t arcs = 0;
-    const RouteIn in = rtt_prepare(c, g, t, 1, st, &sd, &s0, &arcs);
-    if (s0.below_q != ~0ull) {
-        if (res) res->bad_pair = s0.below_q;
-        fail(SRG_ERR_ROUTE, "an edge from node index " + std::to_string(s0.below_q / V) + " to " +
-                                std::to_string(s0.below_q % V) + " is shorter than the table entry of that pair (entry " +
-                                std::to_string(s0.below_q) + "): the table is not a shortest-path table of this graph");
+    const RoutePrep prep = route_prepare(c, g, t, true, st);
+    const RouteIn& in = prep.in;
+    RouteState* sd = prep.state_dev;
+    const uint32_t arcs = prep.arcs;
+    const unsigned long long below = prep.counted.below_q;
+    if (below != ~0ull) {
+        if (res) res->bad_pair = below;
+        fail(SRG_ERR_ROUTE, "an edge from node index " + std::to_string(below / V) + " to " + std::to_string(below % V) +
+                                " is shorter than the table entry of that pair (entry " + std::to_string(below) +
+                                "): the table is not a shortest-path table of this graph");
     }
     const bool lds = V <= srg_env::route_tree_lds_max_v(kRttLdsJumpV);
     const size_t row_bytes = (size_t)V * ((out_pv ? 0 : 4) + (lds ? 0 : 16));
@@ -424,7 +301,7 @@ void route_trees_device(srg_ctx& c, const srg_edge_list* g, const srg_path_table
         rtt_launch_double(lds, V, sources, r0, rows, out_pe + o, pv, scr, out_hops ? out_hops + o : nullptr,
                           out_first ? out_first + o : nullptr, nullptr, in.selfedge, nullptr, sd, st);
     }
-    const RttState s = rtt_read_state(sd, st);
+    const RouteState s = route_read_state(sd, st);
     if (s.bad_arg) fail(SRG_ERR_ARG, "source index out of range (>= n)");
     if (s.bad_q != ~0ull) {
         const uint64_t i = s.bad_q / V;
@@ -463,7 +340,7 @@ void link_loads_trees_device(srg_ctx& c, const srg_edge_list* g, const srg_path_
     uint32_t* nact_dev = (uint32_t*)(nsel + 1);
     size_t sb = 0;
     HIP_CHECK(hipcub::DeviceSelect::If(nullptr, sb, first, active, nact_dev, (int)V, RttRowActive{rownnz}, st));
-    void* stmp = c.b_rtt_tmp.get(sb);
+    void* stmp = c.b_rt_tmp.get(sb);
     HIP_CHECK(hipcub::DeviceSelect::If(stmp, sb, first, active, nact_dev, (int)V, RttRowActive{rownnz}, st));
     unsigned long long head[2] = {0, 0};
     HIP_CHECK(hipMemcpyAsync(head, nsel, 16, hipMemcpyDeviceToHost, st));
@@ -484,28 +361,27 @@ void link_loads_trees_device(srg_ctx& c, const srg_edge_list* g, const srg_path_
     uint32_t* hops = (uint32_t*)c.b_rtt_hops.get((size_t)R * V * 4);
     uint32_t* rowmax = (uint32_t*)c.b_rtt_rowmax.get((size_t)R * 4);
     unsigned long long* scr = lds_jump ? nullptr : (unsigned long long*)c.b_rtt_scr.get((size_t)R * V * 16);
-    uint32_t arcs = 0;
-    auto trees = [&](const RouteIn& in, uint32_t r0, uint32_t rows, RttState* sd) {
+    auto trees = [&](const RoutePrep& p, uint32_t r0, uint32_t rows, RouteState* sd) {
+        const RouteIn& in = p.in;
         HIP_CHECK(hipMemsetAsync(rowmax, 0, (size_t)rows * 4, st));
-        rtt_launch_pred(in, arcs, active, r0, rows, pe, pv, 0, sd, st);
+        rtt_launch_pred(in, p.arcs, active, r0, rows, pe, pv, 0, sd, st);
         rtt_launch_double(lds_jump, V, active, r0, rows, pe, pv, scr, hops, nullptr, cnt, in.selfedge, rowmax, sd, st);
     };
     // The essential lists first.  Where they cannot stand for the full lists -- an edge below its
     // entry, or a nonzero pair they leave unexplained -- the full lists decide, so that this call
     // fails exactly where the pairwise walk does.
     for (int filter = 1; filter >= 0; --filter) {
-        RttState* sd = nullptr;
-        RttState s0;
-        const RouteIn in = rtt_prepare(c, g, t, filter, st, &sd, &s0, &arcs);
-        if (filter && s0.below_q != ~0ull) continue;
+        const RoutePrep prep = route_prepare(c, g, t, filter != 0, st);
+        const RouteIn& in = prep.in;
+        RouteState* sd = prep.state_dev;
+        if (filter && prep.counted.below_q != ~0ull) continue;
         // validate every batch, then commit
-        for (uint32_t r0 = 0; r0 < A; r0 += R) trees(in, r0, std::min(R, A - r0), sd);
-        const RttState s = rtt_read_state(sd, st);
+        for (uint32_t r0 = 0; r0 < A; r0 += R) trees(prep, r0, std::min(R, A - r0), sd);
+        const RouteState s = route_read_state(sd, st);
         if (filter && s.bad_q != ~0ull) continue;
         if (s.noedge_q != ~0ull || s.bad_q != ~0ull) {
-            const RouteState rs{s.bad_q, s.noedge_q, s.total, s.max_hops, 0u, 0u, 0u};
             const uint64_t q = std::min(s.noedge_q, s.bad_q);
-            route_fail_pass0(rs, g, (uint32_t)(q / V), s.bad_q / V, s.bad_q % V, "pair", st, res);
+            route_fail_pass0(s, g, (uint32_t)(q / V), s.bad_q / V, s.bad_q % V, "pair", st, res);
         }
         if (res) {
             res->total_hops = s.total;
@@ -513,7 +389,7 @@ void link_loads_trees_device(srg_ctx& c, const srg_edge_list* g, const srg_path_
         }
         for (uint32_t r0 = 0; r0 < A; r0 += R) {
             const uint32_t rows = std::min(R, A - r0);
-            if (!keep) trees(in, r0, rows, nullptr);
+            if (!keep) trees(prep, r0, rows, nullptr);
             if (lds_sub)
                 k_rtt_push<true><<<rows, kThreads, (size_t)V * 8, st>>>(V, active, r0, pe, pv, hops, rowmax, nullptr, cnt,
                                                                        in.selfedge, g->num_edges,

@@ -16,6 +16,9 @@
 // handed out again at the same address), and a stale list would name wrong edges silently.  The
 // fill order is whatever the atomics give; the walk min-reduces the edge index over all matches,
 // so it does not matter.  The workspace is the context's (b_rt_*), freed by srg_destroy.
+// route_trees.hip.h builds its lists here too: route_prepare(essential = true) keeps only the arcs
+// with lat(e) == D[u][t] (k_rt_csc<., true>) and reports an arc below its entry in
+// RouteState::below_q; the pairwise calls below never ask for that and never set below_q.
 //
 // The walk: one wave64 per query pair; the lanes stride the in-edge list of `cur` in chunks of 64,
 // each gathers D[s][u], L[s][u], reads the entry's lat(e), loss(e) and evaluates the rule; a wave
@@ -27,14 +30,16 @@
 // the walk (latencies >= 1, checked), so it ends; a hop cap of V turns anything else into an error.
 
 struct RouteState {
-    unsigned long long bad_q;     // first query no in-edge explains (loads: s * n + t); ~0 = none
+    unsigned long long bad_q;     // first query no in-edge explains (loads: s * n + t; trees: row * n + t); ~0 = none
     unsigned long long noedge_q;  // first diagonal query whose vertex has no self-loop; ~0 = none
+    unsigned long long below_q;   // essential lists: smallest u * n + t of an arc with lat(e) < D[u][t]; ~0 = none
     unsigned long long total;     // sum of route lengths
     uint32_t max_hops;
-    uint32_t bad_arg;             // a query index >= n
+    uint32_t bad_arg;             // a query (trees: source) index >= n
     uint32_t bad_edge;            // bit 0: an endpoint >= V; bit 1: a non-self-loop edge of latency 0
     uint32_t pad;
 };
+constexpr RouteState kRouteStateInit{~0ull, ~0ull, ~0ull, 0ull, 0u, 0u, 0u, 0u};
 
 struct RouteIn {
     const uint32_t* off;       // [V + 1] in-edge list bounds
@@ -72,16 +77,20 @@ __device__ __forceinline__ uint32_t rt_run_add(uint32_t* __restrict__ ctr, uint3
 // FILL = false: in-degrees into ctr, the smallest self-loop index per vertex, the edge checks.
 // FILL = true: ctr holds the list starts; every arc takes a slot.  (Run only after the checks of
 // the first pass passed: every endpoint is < V and the slots are the counted ones.)
-template <bool FILL>
+// ESSENTIAL (route_trees.hip.h): an arc u -> t is kept only when lat(e) == D[u][t], each orientation
+// of an undirected edge tested on its own (the same predicate in both passes, so the same counts);
+// the first pass flags lat(e) < D[u][t] in below_q.  ESSENTIAL = false reads no table entry.
+template <bool FILL, bool ESSENTIAL>
 __global__ void __launch_bounds__(256) k_rt_csc(uint64_t E, const uint32_t* __restrict__ src,
                                                 const uint32_t* __restrict__ dst, const uint64_t* __restrict__ lat,
                                                 const float* __restrict__ loss, int directed, uint32_t V,
                                                 uint32_t* __restrict__ ctr, uint32_t* __restrict__ ce,
                                                 uint32_t* __restrict__ cu, uint64_t* __restrict__ cl, float* __restrict__ cp,
-                                                uint32_t* __restrict__ selfedge, RouteState* st) {
+                                                uint32_t* __restrict__ selfedge, RouteState* st, PathLatency tab) {
     const uint32_t lane = threadIdx.x & 63;
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     uint32_t bad = 0;
+    unsigned long long below = ~0ull;
     // whole waves stay in the loop together (rt_run_add needs every lane)
     for (size_t e0 = blockIdx.x * (size_t)blockDim.x + (threadIdx.x & ~63u); e0 < E; e0 += stride) {
         const size_t e = e0 + lane;
@@ -96,16 +105,28 @@ __global__ void __launch_bounds__(256) k_rt_csc(uint64_t E, const uint32_t* __re
             if (arc && w == 0) bad |= 2u;
             if (ok && s == t) atomicMin(&selfedge[s], (uint32_t)e);
         }
-        uint32_t p = rt_run_add(ctr, t, arc);
-        if (FILL && arc) {
+        bool keep = arc;
+        if (ESSENTIAL && arc) {
+            const uint64_t d = path_latency(tab, s, t);
+            keep = w == d;
+            if (!FILL && w < d) below = min(below, (unsigned long long)s * V + t);
+        }
+        uint32_t p = rt_run_add(ctr, t, keep);
+        if (FILL && keep) {
             ce[p] = (uint32_t)e;
             cu[p] = s;
             cl[p] = w;
             cp[p] = pl;
         }
         if (!directed) {
-            p = rt_run_add(ctr, s, arc);
-            if (FILL && arc) {
+            keep = arc;
+            if (ESSENTIAL && arc) {
+                const uint64_t d = path_latency(tab, t, s);
+                keep = w == d;
+                if (!FILL && w < d) below = min(below, (unsigned long long)t * V + s);
+            }
+            p = rt_run_add(ctr, s, keep);
+            if (FILL && keep) {
                 ce[p] = (uint32_t)e;
                 cu[p] = t;
                 cl[p] = w;
@@ -113,7 +134,10 @@ __global__ void __launch_bounds__(256) k_rt_csc(uint64_t E, const uint32_t* __re
             }
         }
     }
-    if (!FILL && bad) atomicOr(&st->bad_edge, bad);
+    if (!FILL) {
+        if (bad) atomicOr(&st->bad_edge, bad);
+        if (ESSENTIAL && below != ~0ull) atomicMin(&st->below_q, below);
+    }
 }
 
 __global__ void k_rt_iota(uint32_t* __restrict__ p, uint64_t n) {
@@ -267,50 +291,65 @@ void route_check_table(const srg_edge_list* g, const srg_path_table_dev* t) {
         fail(SRG_ERR_ARG, "graph too large for u32 edge indices (arcs >= 2^32 - 1)");
 }
 
-// The edge checks and the in-edge lists of this call's graph (V >= 1).  Returns after the lists
-// are queued on st; *state_dev is the call's RouteState (reset).
-RouteIn route_prepare(srg_ctx& c, const srg_edge_list* g, const srg_path_table_dev* t, hipStream_t st,
-                      RouteState** state_dev) {
+// The edge checks and the in-edge lists of this call's graph (V >= 1), the essential ones when
+// `essential`.  Synchronises once, after the counting pass; returns with the lists queued on st.
+struct RoutePrep {
+    RouteIn in;
+    RouteState* state_dev;  // the call's RouteState (reset before the counting pass)
+    RouteState counted;     // its value after the counting pass: bad_edge (checked here), below_q
+    uint32_t arcs;
+};
+
+template <bool FILL>
+void route_launch_csc(bool essential, const srg_edge_list* g, const PathLatency& tab, uint32_t* ctr, uint32_t* ce,
+                      uint32_t* cu, uint64_t* cl, float* cp, uint32_t* self, RouteState* sd, hipStream_t st) {
+    const uint64_t E = g->num_edges;
+    if (essential)
+        k_rt_csc<FILL, true><<<grid_for(E, 2048), kThreads, 0, st>>>(E, g->src, g->dst, g->latency_ns, g->packet_loss,
+                                                                    (int)g->directed, g->num_vertices, ctr, ce, cu, cl, cp,
+                                                                    self, sd, tab);
+    else
+        k_rt_csc<FILL, false><<<grid_for(E, 2048), kThreads, 0, st>>>(E, g->src, g->dst, g->latency_ns, g->packet_loss,
+                                                                     (int)g->directed, g->num_vertices, ctr, ce, cu, cl, cp,
+                                                                     self, sd, tab);
+    HIP_CHECK(hipGetLastError());
+}
+
+RoutePrep route_prepare(srg_ctx& c, const srg_edge_list* g, const srg_path_table_dev* t, bool essential,
+                        hipStream_t st) {
     const uint32_t V = g->num_vertices;
     const uint64_t E = g->num_edges;
+    const PathLatency tab{t->latency_ns, t->latency_key, t->diag_ns, t->unit_ns, t->n};
     uint32_t* off = (uint32_t*)c.b_rt_off.get(((size_t)V + 1) * 4);
     uint32_t* cur = (uint32_t*)c.b_rt_cur.get(((size_t)V + 1) * 4);
     uint32_t* self = (uint32_t*)c.b_rt_self.get((size_t)V * 4);
     RouteState* sd = (RouteState*)c.b_rt_state.get(sizeof(RouteState));
-    const RouteState init{~0ull, ~0ull, 0ull, 0u, 0u, 0u, 0u};
-    HIP_CHECK(hipMemcpyAsync(sd, &init, sizeof(RouteState), hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(sd, &kRouteStateInit, sizeof(RouteState), hipMemcpyHostToDevice, st));
     HIP_CHECK(hipMemsetAsync(cur, 0, ((size_t)V + 1) * 4, st));
     HIP_CHECK(hipMemsetAsync(self, 0xFF, (size_t)V * 4, st));
-    if (E)
-        k_rt_csc<false><<<grid_for(E, 2048), kThreads, 0, st>>>(E, g->src, g->dst, g->latency_ns, g->packet_loss,
-                                                               (int)g->directed, V, cur, nullptr, nullptr, nullptr, nullptr,
-                                                               self, sd);
-    HIP_CHECK(hipGetLastError());
+    if (E) route_launch_csc<false>(essential, g, tab, cur, nullptr, nullptr, nullptr, nullptr, self, sd, st);
     size_t tb = 0;
     HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, cur, off, (int)(V + 1), st));
     void* tmp = c.b_rt_tmp.get(tb);
     HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(tmp, tb, cur, off, (int)(V + 1), st));
-    RouteState s0;
-    uint32_t arcs = 0;
-    HIP_CHECK(hipMemcpyAsync(&s0, sd, sizeof(RouteState), hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipMemcpyAsync(&arcs, off + V, 4, hipMemcpyDeviceToHost, st));
+    RoutePrep p{};
+    HIP_CHECK(hipMemcpyAsync(&p.counted, sd, sizeof(RouteState), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(&p.arcs, off + V, 4, hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipStreamSynchronize(st));
-    if (s0.bad_edge & 1) fail(SRG_ERR_ARG, "edge endpoint out of range (>= num_vertices)");
-    if (s0.bad_edge & 2)
+    if (p.counted.bad_edge & 1) fail(SRG_ERR_ARG, "edge endpoint out of range (>= num_vertices)");
+    if (p.counted.bad_edge & 2)
         fail(SRG_ERR_ARG, "an edge between two vertices has latency 0 (the walk's termination rests on latencies >= 1)");
-    uint32_t* ce = (uint32_t*)c.b_rt_ce.get((size_t)arcs * 4);
-    uint32_t* cu = (uint32_t*)c.b_rt_cu.get((size_t)arcs * 4);
-    uint64_t* cl = (uint64_t*)c.b_rt_cl.get((size_t)arcs * 8);
-    float* cp = (float*)c.b_rt_cp.get((size_t)arcs * 4);
-    if (arcs) {
+    uint32_t* ce = (uint32_t*)c.b_rt_ce.get((size_t)p.arcs * 4);
+    uint32_t* cu = (uint32_t*)c.b_rt_cu.get((size_t)p.arcs * 4);
+    uint64_t* cl = (uint64_t*)c.b_rt_cl.get((size_t)p.arcs * 8);
+    float* cp = (float*)c.b_rt_cp.get((size_t)p.arcs * 4);
+    if (p.arcs) {
         HIP_CHECK(hipMemcpyAsync(cur, off, ((size_t)V + 1) * 4, hipMemcpyDeviceToDevice, st));
-        k_rt_csc<true><<<grid_for(E, 2048), kThreads, 0, st>>>(E, g->src, g->dst, g->latency_ns, g->packet_loss,
-                                                              (int)g->directed, V, cur, ce, cu, cl, cp, self, sd);
-        HIP_CHECK(hipGetLastError());
+        route_launch_csc<true>(essential, g, tab, cur, ce, cu, cl, cp, self, sd, st);
     }
-    *state_dev = sd;
-    return RouteIn{off, ce, cu, cl, cp, self,
-                   PathLatency{t->latency_ns, t->latency_key, t->diag_ns, t->unit_ns, t->n}, t->packet_loss, V};
+    p.in = RouteIn{off, ce, cu, cl, cp, self, tab, t->packet_loss, V};
+    p.state_dev = sd;
+    return p;
 }
 
 RouteState route_read_state(RouteState* sd, hipStream_t st) {
@@ -351,12 +390,14 @@ void trace_routes_device(srg_ctx& c, const srg_edge_list* g, const srg_path_tabl
     unsigned long long* offs = (unsigned long long*)c.b_rt_offs.get((nq + 1) * 8);
     HIP_CHECK(hipMemsetAsync(hops, 0, (nq + 1) * 8, st));
     if (V == 0 && nq) fail(SRG_ERR_ARG, "query index out of range (>= n)");
-    RouteState s{~0ull, ~0ull, 0ull, 0u, 0u, 0u, 0u};
+    RouteState s = kRouteStateInit;
     RouteIn in{};
     RouteState* sd = nullptr;
     const uint32_t* perm = nullptr;
     if (nq) {
-        in = route_prepare(c, g, t, st, &sd);
+        const RoutePrep prep = route_prepare(c, g, t, false, st);
+        in = prep.in;
+        sd = prep.state_dev;
         if (nq > 1) {
             // the queries in source order (stable: equal sources keep the caller's order)
             uint32_t* idx = (uint32_t*)c.b_rt_idx.get(nq * 4);
@@ -412,8 +453,9 @@ void link_loads_device(srg_ctx& c, const srg_edge_list* g, const srg_path_table_
     if (N >= 0x7FFFFFFFull) fail(SRG_ERR_ARG, "counts table too large (n * n >= 2^31 - 1)");
     if (N == 0) return;
     const unsigned long long* cnt = (const unsigned long long*)counts;
-    RouteState* sd = nullptr;
-    const RouteIn in = route_prepare(c, g, t, st, &sd);
+    const RoutePrep prep = route_prepare(c, g, t, false, st);
+    const RouteIn& in = prep.in;
+    RouteState* sd = prep.state_dev;
     // the nonzero entries, in row-major order (already grouped by source)
     unsigned long long* nsel = (unsigned long long*)c.b_rt_nsel.get(16);
     HIP_CHECK(hipMemsetAsync(nsel, 0, 16, st));

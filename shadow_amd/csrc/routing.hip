@@ -12,13 +12,14 @@
 // (rank / XCD / scan-group splits), entry_plan.h (the rank row / edge split, the host entry's
 // flags) -- all four without HIP; dense.hip.h (run_dense) and sparse_run.hip.h (run_sparse,
 // choose_sparse), sections of this translation unit; the device headers (kernels, tight_sparse,
-// sparse, sparse_ds, events, xchg); routes.hip.h (route tracing and link loads over a finished
-// table, rule in route_rule.h) and route_trees.hip.h (whole route trees and loads pushed up them,
-// rules in route_tree_rule.h), sections too; h2d_codec.hip.h (the host entry's plain copy, H2D
-// codec and late-loss thread) and host_entry.hip.h (the host entry, stage by stage), the last two
-// sections.  Still here, in order: the validation / W / certify / extract kernels, the context
-// (srg_ctx), prelude(), HostSink, the FW schedules (stream_hop, fw_blocked, SymFw, FwOverlap),
-// compute_device, direct paths, packet events, the event queues, guard(), extern "C".
+// sparse, sparse_ds, events, event_queue, xchg); routes.hip.h (route tracing and link loads over a
+// finished table, rule in route_rule.h) and route_trees.hip.h (whole route trees and loads pushed
+// up them, rules in route_tree_rule.h), sections too; events_run.hip.h (the packet-event batch and
+// event-queue drivers), a section; h2d_codec.hip.h (the host entry's plain copy, H2D codec and
+// late-loss thread) and host_entry.hip.h (the host entry, stage by stage), the last two sections.
+// Still here, in order: the validation / W / certify / extract kernels, the context (srg_ctx),
+// prelude(), HostSink, the FW schedules (stream_hop, fw_blocked, SymFw, FwOverlap),
+// compute_device, direct paths, guard(), device_call(), extern "C".
 // No CPU fallback: every entry point fails loudly (status code) when HIP is unavailable.
 #include <hip/hip_runtime.h>
 #include <hsa/hsa.h>
@@ -855,13 +856,13 @@ struct srg_ctx {
     double ms_create_runtime = 0, ms_create_lib = 0;  // srg_create: HIP runtime / device init vs the library's own
     // packet-event batches (events.hip.h): key / index ping-pong buffers, tile histograms
     DevBuf b_ek0, b_ek1, b_eh0, b_eh1, b_ei0, b_ei1, b_ehist, b_eoffs, b_ered;
-    // routes (routes.hip.h): in-edge lists, walk state, hop counts / offsets, query order, nonzero pairs
+    // routes (routes.hip.h): in-edge lists (route trees build theirs here too), walk state, hop counts / offsets,
+    // query order, nonzero pairs
     DevBuf b_rt_off, b_rt_cur, b_rt_ce, b_rt_cu, b_rt_cl, b_rt_cp, b_rt_self, b_rt_state, b_rt_hops, b_rt_offs, b_rt_idx, b_rt_perm,
         b_rt_keys, b_rt_tmp, b_rt_pairs, b_rt_nsel;
-    // route trees (route_trees.hip.h): essential in-edge lists, state, a batch's predecessors, hops, doubling /
-    // subtree scratch, deepest level per row, the rows with a nonzero count
-    DevBuf b_rtt_off, b_rtt_cur, b_rtt_ce, b_rtt_cu, b_rtt_cl, b_rtt_cp, b_rtt_self, b_rtt_state, b_rtt_tmp, b_rtt_pe, b_rtt_pv,
-        b_rtt_hops, b_rtt_scr, b_rtt_rowmax, b_rtt_rownnz, b_rtt_active, b_rtt_nsel;
+    // route trees (route_trees.hip.h): a batch's predecessors, hops, doubling / subtree scratch, deepest level per
+    // row, the rows with a nonzero count
+    DevBuf b_rtt_pe, b_rtt_pv, b_rtt_hops, b_rtt_scr, b_rtt_rowmax, b_rtt_rownnz, b_rtt_active, b_rtt_nsel;
     int route_tree_rows = 0;            // source rows per batch of the route-tree calls, 0 = by budget (SRG_OPT_ROUTE_TREE_ROWS)
     // Teardown.  The body releases what depends on order; the DevBuf and Event members free
     // themselves afterwards (members are destroyed after the body), so device buffers go last.
@@ -2282,323 +2283,7 @@ void direct_device(srg_ctx& c, const DevGraph& g, const uint32_t* nodes, uint32_
     }
 }
 
-// ---- stretch C5: packet-event batch (events.hip.h) ---------------------------------------
-inline uint32_t bit_width64(uint64_t v) { return v ? 64u - (uint32_t)__builtin_clzll(v) : 0u; }
-
-// status / n_order: a send batch with dropped events (status[i] == 0) -- they are parked behind host
-// num_hosts, and only the n_order sent indices in front of them reach out_order
-template <bool WIDE>
-void events_sort(srg_ctx& c, const EvIn& in, const uint64_t* deliver, const EvKeyFmt& f, uint32_t bits,
-                 uint32_t* out_order, uint64_t* host_off, hipStream_t st, uint32_t& passes,
-                 const uint8_t* status = nullptr, uint64_t n_order = ~0ull) {
-    const uint64_t n = in.n;
-    if (!status) n_order = n;
-    unsigned long long* k0 = (unsigned long long*)c.b_ek0.get(n * 8);
-    unsigned long long* k1 = (unsigned long long*)c.b_ek1.get(n * 8);
-    unsigned long long* h0 = WIDE ? (unsigned long long*)c.b_eh0.get(n * 8) : nullptr;
-    unsigned long long* h1 = WIDE ? (unsigned long long*)c.b_eh1.get(n * 8) : nullptr;
-    uint32_t* i0 = (uint32_t*)c.b_ei0.get(n * 4);
-    uint32_t* i1 = (uint32_t*)c.b_ei1.get(n * 4);
-    if (status) k_ev_keys<WIDE, true><<<grid_for(n, 256 * 64), kThreads, 0, st>>>(in, deliver, f, k0, h0, i0, status);
-    else k_ev_keys<WIDE><<<grid_for(n, 256 * 64), kThreads, 0, st>>>(in, deliver, f, k0, h0, i0);
-    const uint32_t ntiles = (uint32_t)((n + RS_TILE - 1) / RS_TILE);
-    const int nh = (int)(256 * (size_t)ntiles);
-    uint32_t* hist = (uint32_t*)c.b_ehist.get((size_t)nh * 4);
-    uint32_t* offs = (uint32_t*)c.b_eoffs.get((size_t)nh * 4);
-    size_t tb = 0;
-    HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, hist, offs, nh, st));
-    void* tmp = c.b_scantmp.get(tb);
-    passes = 0;
-    for (uint32_t p = 0; p < bits; p += 8) {
-        k_rs_hist<WIDE><<<ntiles, RS_THREADS, 0, st>>>(k0, h0, n, p, ntiles, hist);
-        HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(tmp, tb, hist, offs, nh, st));
-        k_rs_scatter<WIDE><<<ntiles, RS_THREADS, 0, st>>>(k0, h0, i0, k1, h1, i1, n, p, ntiles, hist, offs);
-        std::swap(k0, k1);
-        std::swap(h0, h1);
-        std::swap(i0, i1);
-        ++passes;
-    }
-    HIP_CHECK(hipGetLastError());
-    uint32_t* flag = (uint32_t*)c.b_red.get(64);
-    HIP_CHECK(hipMemsetAsync(flag, 0, 4, st));
-    if (status)
-        k_ev_finish<WIDE, true><<<grid_for(n, 256 * 64), kThreads, 0, st>>>(k0, h0, n, f.sh_dst, in.num_hosts, host_off,
-                                                                              flag);
-    else
-        k_ev_finish<WIDE><<<grid_for(n, 256 * 64), kThreads, 0, st>>>(k0, h0, n, f.sh_dst, in.num_hosts, host_off, flag);
-    HIP_CHECK(hipMemcpyAsync(out_order, i0, n_order * 4, hipMemcpyDeviceToDevice, st));
-    uint32_t hflag = 0;
-    HIP_CHECK(hipMemcpyAsync(&hflag, flag, 4, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    if (hflag)
-        fail(SRG_ERR_EVENT_ORDER,
-             "called `Option::unwrap()` on a `None` value: two packet events with equal (time, src_host_id, "
-             "src_host_event_id) have no relative order");
-}
-
-void order_events_device(srg_ctx& c, const EvIn& in, uint64_t* deliver, uint32_t* out_order, uint64_t* host_off,
-                         hipStream_t st, srg_event_result* res) {
-    if (res) {
-        res->min_next_event_ns = UINT64_MAX;
-        res->min_used_latency_ns = UINT64_MAX;
-        res->key_bits = 0;
-        res->radix_passes = 0;
-    }
-    HIP_CHECK(hipMemsetAsync(host_off, 0, ((size_t)in.num_hosts + 1) * 8, st));
-    if (in.n == 0) {
-        HIP_CHECK(hipStreamSynchronize(st));
-        return;
-    }
-    if (in.n >= 0xFFFFFFFFull) fail(SRG_ERR_ARG, "event batch too large (>= 2^32 events)");
-    EvReduce* red = (EvReduce*)c.b_ered.get(sizeof(EvReduce));
-    EvReduce init{~0ull, 0ull, ~0ull, 0ull, ~0ull, 0u, 0u, 0u, 0u};
-    HIP_CHECK(hipMemcpyAsync(red, &init, sizeof(EvReduce), hipMemcpyHostToDevice, st));
-    k_ev_prep<<<grid_for(in.n, 2048), kThreads, 0, st>>>(in, deliver, red);
-    HIP_CHECK(hipGetLastError());
-    EvReduce r;
-    HIP_CHECK(hipMemcpyAsync(&r, red, sizeof(EvReduce), hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    if (r.bad & 2) fail(SRG_ERR_ARG, "event node position out of range (>= table_n)");
-    if (r.bad & 1) fail(SRG_ERR_ARG, "event dst_host out of range (>= num_hosts)");
-    if (r.bad & 4) fail(SRG_ERR_LATENCY_RANGE, "deliver time overflows EmulatedTime (send + latency)");
-    EvKeyFmt f{};
-    const uint32_t b_id = bit_width64(r.id_max - r.id_min), b_src = bit_width64(r.src_max),
-                   b_t = bit_width64(r.t_max - r.t_min), b_dst = bit_width64(r.dst_max);
-    f.t_min = r.t_min;
-    f.id_min = r.id_min;
-    f.sh_src = b_id;
-    f.sh_t = b_id + b_src;
-    f.sh_dst = b_id + b_src + b_t;
-    const uint32_t bits = f.sh_dst + b_dst;
-    if (bits > 128) fail(SRG_ERR_ARG, "event batch key wider than 128 bits");
-    uint32_t passes = 0;
-    // an all-equal key (bits == 0) needs no pass; a 1-event batch is trivially ordered
-    if (bits <= 64) events_sort<false>(c, in, deliver, f, bits, out_order, host_off, st, passes);
-    else events_sort<true>(c, in, deliver, f, bits, out_order, host_off, st, passes);
-    if (res) {
-        res->min_next_event_ns = r.t_min;
-        res->min_used_latency_ns = r.lat_min;
-        res->key_bits = bits;
-        res->radix_passes = passes;
-    }
-}
-
-// The whole per-packet tail of send_packet (srg_send_packets_device): order_events_device with the
-// drop decision in front, either table form, and the packet counters.
-void send_packets_device(srg_ctx& c, const EvIn& in, const EvSendIn& sx, uint8_t* status, uint64_t* deliver,
-                         uint32_t* out_order, uint64_t* host_off, unsigned long long* counts, hipStream_t st,
-                         srg_send_result* res) {
-    if (res) {
-        res->ev.min_next_event_ns = UINT64_MAX;
-        res->ev.min_used_latency_ns = UINT64_MAX;
-        res->ev.key_bits = 0;
-        res->ev.radix_passes = 0;
-        res->num_sent = res->num_dropped = 0;
-    }
-    HIP_CHECK(hipMemsetAsync(host_off, 0, ((size_t)in.num_hosts + 1) * 8, st));
-    if (in.n == 0) {
-        HIP_CHECK(hipStreamSynchronize(st));
-        return;
-    }
-    if (in.n >= 0xFFFFFFFFull) fail(SRG_ERR_ARG, "event batch too large (>= 2^32 events)");
-    if (in.num_hosts == UINT32_MAX) fail(SRG_ERR_ARG, "num_hosts too large (host 2^32 - 1 parks the dropped events)");
-    EvSendReduce* red = (EvSendReduce*)c.b_ered.get(sizeof(EvSendReduce));
-    EvSendReduce init{{~0ull, 0ull, ~0ull, 0ull, ~0ull, 0u, 0u, 0u, 0u}, 0ull};
-    HIP_CHECK(hipMemcpyAsync(red, &init, sizeof(EvSendReduce), hipMemcpyHostToDevice, st));
-    k_ev_send_prep<<<grid_for(in.n, 2048), kThreads, 0, st>>>(in, sx, status, deliver, red);
-    HIP_CHECK(hipGetLastError());
-    EvSendReduce sr;
-    HIP_CHECK(hipMemcpyAsync(&sr, red, sizeof(EvSendReduce), hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    const EvReduce& r = sr.r;
-    if (r.bad & 2) fail(SRG_ERR_ARG, "event node position out of range (>= table n)");
-    if (r.bad & 1) fail(SRG_ERR_ARG, "event dst_host out of range (>= num_hosts)");
-    if (r.bad & 4) fail(SRG_ERR_LATENCY_RANGE, "deliver time overflows EmulatedTime (send + latency)");
-    const uint64_t sent = sr.sent, drops = in.n - sent;
-    // the counters move once the range checks passed (every index is inside the table), as
-    // increment_packet_count runs at the send, before any queue is popped
-    if (counts && sent) {
-        k_ev_counts<<<grid_for(in.n, 2048), kThreads, 0, st>>>(in, status, counts);
-        HIP_CHECK(hipGetLastError());
-    }
-    uint32_t bits = 0, passes = 0;
-    if (sent) {
-        EvKeyFmt f{};
-        // dropped events are parked behind host num_hosts: the host field must hold that value
-        const uint32_t b_id = bit_width64(r.id_max - r.id_min), b_src = bit_width64(r.src_max),
-                       b_t = bit_width64(r.t_max - r.t_min), b_dst = bit_width64(drops ? in.num_hosts : r.dst_max);
-        f.t_min = r.t_min;
-        f.id_min = r.id_min;
-        f.sh_src = b_id;
-        f.sh_t = b_id + b_src;
-        f.sh_dst = b_id + b_src + b_t;
-        bits = f.sh_dst + b_dst;
-        if (bits > 128) fail(SRG_ERR_ARG, "event batch key wider than 128 bits");
-        const uint8_t* parked = drops ? status : nullptr;
-        if (bits <= 64) events_sort<false>(c, in, deliver, f, bits, out_order, host_off, st, passes, parked, sent);
-        else events_sort<true>(c, in, deliver, f, bits, out_order, host_off, st, passes, parked, sent);
-    } else {
-        HIP_CHECK(hipStreamSynchronize(st));
-    }
-    if (res) {
-        res->ev.min_next_event_ns = r.t_min;
-        res->ev.min_used_latency_ns = r.lat_min;
-        res->ev.key_bits = bits;
-        res->ev.radix_passes = passes;
-        res->num_sent = sent;
-        res->num_dropped = drops;
-    }
-}
-
-}  // namespace
-
-// ---- device-resident per-host event queues (event_queue.hip.h) ---------------------------
-// Two sets of resident arrays: `cur` is the queues, the other one is where a push builds the
-// merged result; it becomes `cur` only after the device flags were read (an error leaves the
-// queues as they were).  A set that is too small is simply reallocated before it is built into:
-// the contents live in the other one.
-struct srg_event_queues {
-    srg_ctx* ctx = nullptr;
-    uint32_t num_hosts = 0;
-    struct Set {
-        DevBuf k0, k1, k2, tag, host_off, head;
-        uint64_t cap = 0;
-        EvqSet ptrs() const { return EvqSet{(uint64_t*)k0.p, (uint64_t*)k1.p, (uint64_t*)k2.p, (uint64_t*)tag.p}; }
-        void reserve(uint64_t n) {
-            if (n <= cap) return;
-            const uint64_t want = std::max(n, 2 * cap);
-            cap = 0;  // (a failed allocation leaves the set empty, not half grown)
-            for (DevBuf* b : {&k0, &k1, &k2, &tag}) b->get(want * 8);
-            cap = want;
-        }
-    } set[2];
-    int cur = 0;
-    DevBuf last_popped, bk0, bk1, bk2, btag, dead, dead_excl, part_a, part_live, new_head, cnt, offs, state, scantmp;
-    uint64_t stored = 0;  // events in the current set's arrays, popped ones included
-    uint64_t live = 0;
-    uint64_t min_next = UINT64_MAX;
-};
-
-namespace {
-
-void evq_fill_result(const srg_event_queues& q, uint64_t moved, srg_queue_result* res) {
-    if (!res) return;
-    res->num_moved = moved;
-    res->num_queued = q.live;
-    res->min_next_event_ns = q.min_next;
-}
-
-void evq_scan(srg_event_queues& q, const uint64_t* in, uint64_t* out, hipStream_t st) {
-    const int n = (int)q.num_hosts + 1;
-    size_t tb = 0;
-    HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, in, out, n, st));
-    void* tmp = q.scantmp.get(tb);
-    HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(tmp, tb, in, out, n, st));
-}
-
-EvqState evq_read_state(EvqState* dev, hipStream_t st) {
-    EvqState s;
-    HIP_CHECK(hipMemcpyAsync(&s, dev, sizeof(EvqState), hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    return s;
-}
-
-void evq_push(srg_event_queues& q, const srg_event_batch* b, const uint64_t* deliver, const uint32_t* order,
-              uint64_t nb, const uint64_t* tag, hipStream_t st, srg_queue_result* res) {
-    evq_fill_result(q, 0, res);
-    if (nb == 0) return;  // nothing to merge: the queues (their popped prefixes too) stay as they are
-    if (nb > b->num_events) fail(SRG_ERR_ARG, "num_order exceeds the batch's num_events");
-    if (b->num_events >= 0xFFFFFFFFull) fail(SRG_ERR_ARG, "event batch too large (>= 2^32 events)");
-    const uint32_t H = q.num_hosts;
-    srg_event_queues::Set& A = q.set[q.cur];
-    srg_event_queues::Set& O = q.set[q.cur ^ 1];
-    const EvqSet B{(uint64_t*)q.bk0.get(nb * 8), (uint64_t*)q.bk1.get(nb * 8), (uint64_t*)q.bk2.get(nb * 8),
-                   (uint64_t*)q.btag.get(nb * 8)};
-    EvqState* ds = (EvqState*)q.state.get(sizeof(EvqState));
-    const EvqState init{~0ull, 0u, 0u};
-    HIP_CHECK(hipMemcpyAsync(ds, &init, sizeof(EvqState), hipMemcpyHostToDevice, st));
-    const EvqGatherIn gi{b->num_events, nb, order, b->dst_host, b->src_host, b->src_event_id, deliver, tag, H};
-    k_evq_gather<<<grid_for(nb, 2048), kThreads, 0, st>>>(gi, B, (const uint64_t*)q.last_popped.p, ds);
-    HIP_CHECK(hipGetLastError());
-    EvqState s = evq_read_state(ds, st);
-    if (s.flags & EVQ_BAD_ORDER)
-        fail(SRG_ERR_ARG,
-             "order is not the batch's queue order (an entry >= num_events, a dst_host >= num_hosts, or keys "
-             "not strictly increasing by dst_host, time, src_host, event id)");
-    if (s.flags & EVQ_TIME_BACKWARD)
-        fail(SRG_ERR_TIME_BACKWARD,
-             "assertion failed: event.time() >= self.last_popped_event_time: a pushed event is earlier than "
-             "its host's last popped event");
-    const uint64_t n_out = q.live + nb, n = q.stored + nb;
-    O.reserve(n_out);
-    const uint64_t* a_off = (const uint64_t*)A.host_off.p;
-    const uint64_t* a_head = (const uint64_t*)A.head.p;
-    uint64_t* dead = (uint64_t*)q.dead.p;
-    uint64_t* dead_excl = (uint64_t*)q.dead_excl.p;
-    k_evq_dead<<<grid_for((size_t)H + 1), kThreads, 0, st>>>(a_off, a_head, H, dead);
-    evq_scan(q, dead, dead_excl, st);
-    const uint64_t ntiles = (n + EVQ_TILE - 1) / EVQ_TILE;
-    if (ntiles >= 0x7FFFFFFFull) fail(SRG_ERR_ARG, "event queues too large for one merge launch");
-    uint64_t* part_a = (uint64_t*)q.part_a.get((ntiles + 1) * 8);
-    uint64_t* part_live = (uint64_t*)q.part_live.get((ntiles + 1) * 8);
-    k_evq_partition<<<grid_for(ntiles + 1), kThreads, 0, st>>>(A.ptrs(), q.stored, B, nb, a_off, a_head, dead_excl, H,
-                                                                ntiles, part_a, part_live);
-    k_evq_merge<<<(unsigned)ntiles, EVQ_THREADS, 0, st>>>(A.ptrs(), B, n, part_a, part_live, a_head, O.ptrs(), n_out, ds);
-    k_evq_finish<<<grid_for(n_out, 2048), kThreads, 0, st>>>((const uint64_t*)O.k0.p, n_out, H, (uint64_t*)O.host_off.p,
-                                                             (uint64_t*)O.head.p);
-    k_evq_min<<<grid_for(H, 2048), kThreads, 0, st>>>(O.ptrs(), (const uint64_t*)O.host_off.p,
-                                                      (const uint64_t*)O.head.p, H, ds);
-    HIP_CHECK(hipGetLastError());
-    s = evq_read_state(ds, st);
-    if (s.flags & EVQ_EQUAL_KEYS)
-        fail(SRG_ERR_EVENT_ORDER,
-             "called `Option::unwrap()` on a `None` value: two packet events with equal (time, src_host_id, "
-             "src_host_event_id) have no relative order");
-    q.cur ^= 1;
-    q.stored = q.live = n_out;
-    q.min_next = s.min_head;
-    evq_fill_result(q, nb, res);
-}
-
-void evq_pop(srg_event_queues& q, uint64_t until, uint64_t capacity, uint64_t* out_time, uint32_t* out_src,
-             uint64_t* out_id, uint64_t* out_tag, uint64_t* out_off, hipStream_t st, srg_queue_result* res) {
-    evq_fill_result(q, 0, res);
-    const uint32_t H = q.num_hosts;
-    srg_event_queues::Set& A = q.set[q.cur];
-    uint64_t* host_off = (uint64_t*)A.host_off.p;
-    uint64_t* head = (uint64_t*)A.head.p;
-    uint64_t* new_head = (uint64_t*)q.new_head.p;
-    uint64_t* cnt = (uint64_t*)q.cnt.p;
-    uint64_t* offs = (uint64_t*)q.offs.p;
-    k_evq_pop_find<<<grid_for((size_t)H + 1, 2048), kThreads, 0, st>>>(A.ptrs(), host_off, head, H, until, new_head, cnt);
-    HIP_CHECK(hipGetLastError());
-    evq_scan(q, cnt, offs, st);
-    uint64_t total = 0;
-    HIP_CHECK(hipMemcpyAsync(&total, offs + H, 8, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    if (total > capacity) {
-        if (res) res->num_moved = total;
-        fail(SRG_ERR_ARG, "out_capacity too small: " + std::to_string(total) + " events are due (nothing popped)");
-    }
-    if (out_off) HIP_CHECK(hipMemcpyAsync(out_off, offs, ((size_t)H + 1) * 8, hipMemcpyDeviceToDevice, st));
-    if (total == 0) {
-        HIP_CHECK(hipStreamSynchronize(st));
-        return;
-    }
-    EvqState* ds = (EvqState*)q.state.get(sizeof(EvqState));
-    const EvqState init{~0ull, 0u, 0u};
-    HIP_CHECK(hipMemcpyAsync(ds, &init, sizeof(EvqState), hipMemcpyHostToDevice, st));
-    k_evq_pop_copy<<<grid_for(total, 2048), kThreads, 0, st>>>(A.ptrs(), head, offs, H, total, out_time, out_src, out_id,
-                                                               out_tag);
-    k_evq_pop_commit<<<grid_for(H, 2048), kThreads, 0, st>>>(A.ptrs(), host_off, head, (uint64_t*)q.last_popped.p,
-                                                             new_head, H, ds);
-    HIP_CHECK(hipGetLastError());
-    const EvqState s = evq_read_state(ds, st);
-    q.live -= total;
-    q.min_next = s.min_head;
-    evq_fill_result(q, total, res);
-}
-
+#include "events_run.hip.h"
 #include "h2d_codec.hip.h"
 
 int guard(char* errbuf, size_t errlen, const std::function<void()>& body) {
@@ -2622,6 +2307,22 @@ int guard(char* errbuf, size_t errlen, const std::function<void()>& body) {
         set_err(errbuf, errlen, "internal error");
         return SRG_ERR_INTERNAL;
     }
+}
+
+// A device call of the C ABI, after its null checks: under ctx->mu, on the context's device,
+// body(st) with the caller's stream or the context's.  *ms_total (when given) is the wall time from
+// here to the return, of a failed call too.  The stream is not synchronised here: every body does
+// that itself on each path that queued work.
+template <class F>
+int device_call(srg_ctx* ctx, void* hip_stream, double* ms_total, char* errbuf, size_t errlen, F&& body) {
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    auto t0 = std::chrono::steady_clock::now();
+    const int rc = guard(errbuf, errlen, [&]() {
+        HIP_CHECK(hipSetDevice(ctx->device));
+        body(hip_stream ? (hipStream_t)hip_stream : ctx->stream);
+    });
+    if (ms_total) *ms_total = ms_since(t0);
+    return rc;
 }
 
 #include "host_entry.hip.h"
@@ -3304,16 +3005,10 @@ int srg_order_packet_events_device(srg_ctx* ctx, const srg_event_batch* b, const
         set_err(errbuf, errlen, "null argument");
         return SRG_ERR_ARG;
     }
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    return guard(errbuf, errlen, [&]() {
-        auto t0 = std::chrono::steady_clock::now();
-        HIP_CHECK(hipSetDevice(ctx->device));
-        hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+    return device_call(ctx, hip_stream, res ? &res->ms_total : nullptr, errbuf, errlen, [&](hipStream_t st) {
         EvIn in{b->num_events, b->src_node, b->dst_node, b->src_host, b->dst_host, b->send_time_ns,
                 b->src_event_id, table, table_n, b->num_hosts, b->round_end_ns};
-        order_events_device(*ctx, in, out_deliver, out_order, out_host_off, st, res);
-        HIP_CHECK(hipStreamSynchronize(st));
-        if (res) res->ms_total = ms_since(t0);
+        event_batch_device<false>(*ctx, in, EvSendIn{}, nullptr, out_deliver, out_order, out_host_off, nullptr, st, res);
     });
 }
 
@@ -3342,19 +3037,18 @@ int srg_send_packets_device(srg_ctx* ctx, const srg_send_batch* sb, const srg_pa
         set_err(errbuf, errlen, "send batch: chance and payload_size are required with a packet_loss table");
         return SRG_ERR_ARG;
     }
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    return guard(errbuf, errlen, [&]() {
-        auto t0 = std::chrono::steady_clock::now();
-        HIP_CHECK(hipSetDevice(ctx->device));
-        hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+    return device_call(ctx, hip_stream, res ? &res->ev.ms_total : nullptr, errbuf, errlen, [&](hipStream_t st) {
         EvIn in{b->num_events, b->src_node, b->dst_node, b->src_host, b->dst_host, b->send_time_ns,
                 b->src_event_id, nullptr, t->n, b->num_hosts, b->round_end_ns};
         EvSendIn sx{{t->latency_ns, t->latency_key, t->diag_ns, t->unit_ns, t->n}, t->packet_loss, sb->chance,
                     sb->payload_size, sb->bootstrap_end_ns};
-        send_packets_device(*ctx, in, sx, out_status, out_deliver, out_order, out_host_off,
-                            (unsigned long long*)packet_counts, st, res);
-        HIP_CHECK(hipStreamSynchronize(st));
-        if (res) res->ev.ms_total = ms_since(t0);
+        if (res) res->num_sent = res->num_dropped = 0;
+        const uint64_t sent = event_batch_device<true>(*ctx, in, sx, out_status, out_deliver, out_order, out_host_off,
+                                                       (unsigned long long*)packet_counts, st, res ? &res->ev : nullptr);
+        if (res) {
+            res->num_sent = sent;
+            res->num_dropped = b->num_events - sent;
+        }
     });
 }
 
@@ -3404,17 +3098,8 @@ int srg_event_queues_push_device(srg_event_queues* q, const srg_event_batch* b, 
         set_err(errbuf, errlen, "null argument");
         return SRG_ERR_ARG;
     }
-    srg_ctx* ctx = q->ctx;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    return guard(errbuf, errlen, [&]() {
-        auto t0 = std::chrono::steady_clock::now();
-        HIP_CHECK(hipSetDevice(ctx->device));
-        hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
-        if (res) res->ms_total = 0;
-        evq_push(*q, b, deliver, order, num_order, tag, st, res);
-        HIP_CHECK(hipStreamSynchronize(st));
-        if (res) res->ms_total = ms_since(t0);
-    });
+    return device_call(q->ctx, hip_stream, res ? &res->ms_total : nullptr, errbuf, errlen,
+                       [&](hipStream_t st) { evq_push(*q, b, deliver, order, num_order, tag, st, res); });
 }
 
 int srg_event_queues_pop_device(srg_event_queues* q, uint64_t until_ns, uint64_t out_capacity, uint64_t* out_time,
@@ -3424,16 +3109,8 @@ int srg_event_queues_pop_device(srg_event_queues* q, uint64_t until_ns, uint64_t
         set_err(errbuf, errlen, "null argument");
         return SRG_ERR_ARG;
     }
-    srg_ctx* ctx = q->ctx;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    return guard(errbuf, errlen, [&]() {
-        auto t0 = std::chrono::steady_clock::now();
-        HIP_CHECK(hipSetDevice(ctx->device));
-        hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
-        if (res) res->ms_total = 0;
+    return device_call(q->ctx, hip_stream, res ? &res->ms_total : nullptr, errbuf, errlen, [&](hipStream_t st) {
         evq_pop(*q, until_ns, out_capacity, out_time, out_src, out_id, out_tag, out_off, st, res);
-        HIP_CHECK(hipStreamSynchronize(st));
-        if (res) res->ms_total = ms_since(t0);
     });
 }
 
@@ -3445,15 +3122,9 @@ int srg_trace_routes_device(srg_ctx* ctx, const srg_edge_list* g, const srg_path
         set_err(errbuf, errlen, "null argument");
         return SRG_ERR_ARG;
     }
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    auto t0 = std::chrono::steady_clock::now();
-    const int rc = guard(errbuf, errlen, [&]() {
-        HIP_CHECK(hipSetDevice(ctx->device));
-        hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+    return device_call(ctx, hip_stream, res ? &res->ms_total : nullptr, errbuf, errlen, [&](hipStream_t st) {
         trace_routes_device(*ctx, g, t, src, dst, num_pairs, hop_capacity, out_off, out_edge, out_vertex, st, res);
     });
-    if (res) res->ms_total = ms_since(t0);
-    return rc;
 }
 
 int srg_link_loads_device(srg_ctx* ctx, const srg_edge_list* g, const srg_path_table_dev* t, const uint64_t* counts,
@@ -3463,15 +3134,9 @@ int srg_link_loads_device(srg_ctx* ctx, const srg_edge_list* g, const srg_path_t
         set_err(errbuf, errlen, "null argument");
         return SRG_ERR_ARG;
     }
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    auto t0 = std::chrono::steady_clock::now();
-    const int rc = guard(errbuf, errlen, [&]() {
-        HIP_CHECK(hipSetDevice(ctx->device));
-        hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+    return device_call(ctx, hip_stream, res ? &res->ms_total : nullptr, errbuf, errlen, [&](hipStream_t st) {
         link_loads_device(*ctx, g, t, counts, edge_packets, st, res);
     });
-    if (res) res->ms_total = ms_since(t0);
-    return rc;
 }
 
 int srg_route_trees_device(srg_ctx* ctx, const srg_edge_list* g, const srg_path_table_dev* t, const uint32_t* sources,
@@ -3482,16 +3147,10 @@ int srg_route_trees_device(srg_ctx* ctx, const srg_edge_list* g, const srg_path_
         set_err(errbuf, errlen, "null argument");
         return SRG_ERR_ARG;
     }
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    auto t0 = std::chrono::steady_clock::now();
-    const int rc = guard(errbuf, errlen, [&]() {
-        HIP_CHECK(hipSetDevice(ctx->device));
-        hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+    return device_call(ctx, hip_stream, res ? &res->ms_total : nullptr, errbuf, errlen, [&](hipStream_t st) {
         route_trees_device(*ctx, g, t, sources, num_sources, out_pred_edge, out_pred_vertex, out_hops, out_first_edge,
                            st, res);
     });
-    if (res) res->ms_total = ms_since(t0);
-    return rc;
 }
 
 int srg_link_loads_trees_device(srg_ctx* ctx, const srg_edge_list* g, const srg_path_table_dev* t,
@@ -3501,15 +3160,9 @@ int srg_link_loads_trees_device(srg_ctx* ctx, const srg_edge_list* g, const srg_
         set_err(errbuf, errlen, "null argument");
         return SRG_ERR_ARG;
     }
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    auto t0 = std::chrono::steady_clock::now();
-    const int rc = guard(errbuf, errlen, [&]() {
-        HIP_CHECK(hipSetDevice(ctx->device));
-        hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+    return device_call(ctx, hip_stream, res ? &res->ms_total : nullptr, errbuf, errlen, [&](hipStream_t st) {
         link_loads_trees_device(*ctx, g, t, counts, edge_packets, st, res);
     });
-    if (res) res->ms_total = ms_since(t0);
-    return rc;
 }
 
 int srg_next_window(uint64_t min_next_event_ns, uint64_t runahead_ns, uint64_t end_time_ns, uint64_t* window_start_ns,

@@ -1,5 +1,5 @@
 // send_rule.h — the per-packet decisions of Worker::send_packet that the send batch makes on the
-// device, shared by the kernel (k_ev_send_prep, events.hip.h) and a CPU unit test
+// device, shared by the kernel (k_ev_prep<true>, events.hip.h) and a CPU unit test
 // (tests/cpp/send_rule_check.cpp, built with g++).
 //
 // Reference, src/main/core/worker.rs:

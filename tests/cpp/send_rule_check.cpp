@@ -1,4 +1,4 @@
-// CPU check of shadow_amd/csrc/send_rule.h (the same header k_ev_send_prep includes): the drop
+// CPU check of shadow_amd/csrc/send_rule.h (the same header k_ev_prep<true> includes): the drop
 // predicate of Worker::send_packet (worker.rs:374-390, 563-568) and the latency fetch from either
 // table form, on hand-written cases.  Prints "ok" and exits 0, or names the first failing case.
 #include <cmath>

@@ -447,7 +447,63 @@ def test_send_packets_counts_feed_tree_loads(router):
     assert np.array_equal(got, want) and int(got.sum()) == volume
 
 
-# ---- 10. the other kernel paths --------------------------------------------------------------------
+# ---- 10. one workspace for both call families -----------------------------------------------------------
+def loads_from_trees(ref, num_edges, counts):
+    """Every off-diagonal count added along its route of the reference trees (pred_edge, pred_vertex)."""
+    pe, pv = ref[0], ref[1]
+    out = np.zeros(num_edges, np.uint64)
+    for s, t in zip(*np.nonzero(counts)):
+        c = counts[s, t]
+        while t != s:
+            out[pe[s, t]] += c
+            t = pv[s, t]
+    return out
+
+
+def test_route_and_tree_calls_share_one_workspace(router):
+    """The pairwise calls and the tree calls build their in-edge lists in the same buffers of the
+    context.  Calls of both families on one router, over graphs of different size and direction, the
+    essential lists and the full ones in turn: each result is that of the cached reference.  Step 3
+    raises one table entry above the edge that carries it (the edge then lies below its entry), which
+    makes the loads call drop the essential lists and build the full ones, and makes a trees call
+    fail as test_edge_below_its_entry_is_refused expects."""
+    big, _, _, big_table, big_ref = case(router, "bip10_140")
+    # 1. essential lists of 150 vertices
+    assert_trees(routes.route_trees(router, big, big_table)[:4], big_ref)
+    # 2. full lists of a smaller, directed graph: every pair's route against the trees
+    e, _, _, table, ref = case(router, "rand12_directed")
+    V = e.num_vertices
+    offd = ~np.eye(V, dtype=bool)
+    pairs = R.all_pairs(V)[offd.reshape(-1)]
+    off, he, hv, _ = routes.trace_routes(router, e, table, pairs)
+    off = off.astype(np.int64)
+    assert np.array_equal(ref[2][offd], np.diff(off))
+    assert np.array_equal(ref[0][offd], he[off[1:] - 1]) and np.array_equal(ref[3][offd], he[off[:-1]])
+    # 3. an edge below its entry: the essential lists are built, refused, and the full lists rebuilt
+    e, lat, loss, _, ref = case(router, "rand11")
+    V = e.num_vertices
+    s, t = next((s, t) for s in range(V) for t in range(V)
+                if t != s and ref[1][s][t] == s and not (ref[1][s] == t).any() and e.latency_ns[ref[0][s][t]] == lat[s, t])
+    bad = damaged(lat, loss, s, t, "latency")
+    counts = sparse_counts(V, 78, 500, diag=0)
+    np.fill_diagonal(counts, 0)
+    counts[s, t] = 0
+    got, res = routes.link_loads_trees(router, e, bad, counts)
+    assert np.array_equal(got, loads_from_trees(ref, e.num_edges, counts)) and res["bad_pair"] == U64_MAX
+    rc, res, msg, _ = raw_trees(router, e, bad, [0])
+    assert rc == N.SRG_ERR_ROUTE and res["bad_pair"] == s * V + t, msg
+    assert "from node index %d to %d " % (s, t) in msg and "shorter than the table entry" in msg
+    # 4. the pairwise loads, full lists of the large graph again
+    counts = sparse_counts(big.num_vertices, 79, 300, diag=0)
+    np.fill_diagonal(counts, 0)
+    got, res = routes.link_loads(router, big, big_table, counts)
+    assert np.array_equal(got, loads_from_trees(big_ref, big.num_edges, counts))
+    assert res["num_pairs"] == int((counts != 0).sum())
+    # 5. and its essential lists again
+    assert_trees(routes.route_trees(router, big, big_table)[:4], big_ref)
+
+
+# ---- 11. the other kernel paths --------------------------------------------------------------------
 @pytest.mark.parametrize("name", ["chain200", "bip10_140", "rand14_ties"])
 def test_global_scratch_paths_and_wave_per_target(router, monkeypatch, name):
     """SRG_ROUTE_TREE_LDS_MAX_V=0 sends a small graph down the global-scratch doubling and push of a

@@ -1,5 +1,5 @@
 """The whole per-packet tail of Worker::send_packet as one batch (srg_send_packets_device,
-events.hip.h k_ev_send_prep / k_ev_counts): drop decision, latency from either table form, deliver
+events.hip.h k_ev_prep<true> / k_ev_counts): drop decision, latency from either table form, deliver
 times, per-host pop order, packet counts.  Every comparison is exact (integers) against the numpy
 restatement below of worker.rs:374-424, event.rs:84-155 and mod.rs:449-456."""
 import numpy as np

@@ -1,5 +1,5 @@
 """CPU check of the send batch's decision rule (shadow_amd/csrc/send_rule.h, included by
-k_ev_send_prep): tests/cpp/send_rule_check.cpp feeds it the drop boundary at loss 0.25, loss 0 and
+k_ev_prep<true>): tests/cpp/send_rule_check.cpp feeds it the drop boundary at loss 0.25, loss 0 and
 1, payload 0, the bootstrap boundary, a loss whose f32 reliability rounds to 1 (the f32-then-widen
 order of worker.rs:563-568) and both table forms of the latency fetch.  The GPU side of the same
 header: tests/test_send_packets_gpu.py."""

@@ -30,8 +30,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-PREP_BYTES = 48    # k_ev_prep per event
-EXTRA_BYTES = 17   # k_ev_send_prep on top of it
+PREP_BYTES = 48    # k_ev_prep<false> per event
+EXTRA_BYTES = 17   # k_ev_prep<true> (the send call) on top of it
 
 
 def kernel_avg_us(path):
@@ -137,10 +137,10 @@ def main():
     pairs, sent = distinct_pairs_per_wave(b, status, H)
 
     kern = kernel_avg_us(args.kernel_stats) if args.kernel_stats else {}
-    prep_us = kern.get("k_ev_prep")
+    prep_us = kern.get("k_ev_prep<false>")
     if prep_us:
         rate = PREP_BYTES * n / (prep_us * 1e-6)
-        rate_src = "k_ev_prep in the kernel trace"
+        rate_src = "k_ev_prep<false> in the kernel trace"
     else:
         rate, rate_src = 8e12, "no kernel trace given: the HBM peak of 8 TB/s (the tightest allowance)"
     spread = stat["a"]["max_ms"] - stat["a"]["min_ms"]
