@@ -553,6 +553,78 @@ int srg_event_queues_pop_device(srg_event_queues* q, uint64_t until_ns, uint64_t
 int srg_next_window(uint64_t min_next_event_ns, uint64_t runahead_ns, uint64_t end_time_ns,
                     uint64_t* window_start_ns, uint64_t* window_end_ns);
 
+/* ---- the hosts' inbound path: CoDel router queue, token-bucket relay -------------------------
+ * What every popped packet event begins with on its host (host.rs:853-858):
+ *   router.route_incoming_packet(packet) -> CoDelQueue::push(packet, now)
+ *                                              router/mod.rs:59-61, codel_queue.rs:305-319
+ *   notify_router_has_packets()          -> relay_inet_in.notify(host)   host.rs:992-994, relay/mod.rs:111-136
+ *   forward task -> forward_until_blocked: CoDelQueue::pop(now), TokenBucket::comforming_remove(total_size)
+ *                                              relay/mod.rs:201-273, token_bucket.rs:68-157
+ * kept per host in HBM across steps: the bucket (refill max(1, bw_down_bits / 8 / 1000) per 1 ms,
+ * capacity refill + 1500, created full; bw_down_bits == UINT64_MAX is RateLimit::Unlimited), the
+ * CoDel state (TARGET 10 ms, INTERVAL 100 ms, no length limit), the relay (Idle / Pending, one
+ * cached packet) and the router queue's packets.  Per host: an arrival at t is enqueued with
+ * enqueue_ts = t and, if the relay is Idle, schedules a forward task at t; a task at T runs after
+ * every arrival with time <= T (Packet before Local, event.rs:103-110); before bootstrap_end_ns
+ * the bucket is not touched.  A step processes every given arrival and every forward task with
+ * time < until_ns; a task at exactly until_ns stays pending.
+ *   Domain: sim_start_ns <= every time < 2^62, until_ns <= 2^62; outside it, offsets that are not
+ *        monotone from 0 to num_arrivals, or an arrival time >= until_ns: SRG_ERR_ARG
+ *   a packet larger than a limited host's bucket capacity: SRG_ERR_ARG (the balance is clamped to
+ *        the capacity, so the reference's relay would reschedule itself every refill for ever;
+ *        Shadow's packets are at most CONFIG_MTU and never get there)
+ *   an arrival earlier than its host's previous arrival or its last executed task:
+ *        SRG_ERR_TIME_BACKWARD
+ * Outputs are grouped by host (increasing HostId), each host's packets in the order they left,
+ * forwards (status 1, at the task's time) and CoDel drops (status 0, the time of the task that
+ * dropped them) interleaved as they occurred.  With out_capacity 0 every output may be NULL; more
+ * packets leaving than out_capacity: SRG_ERR_ARG, num_forwarded + num_dropped = the count needed,
+ * nothing changed; (num_queued before the call) + num_arrivals always suffices.  Any call that
+ * returns an error leaves the state exactly as it was.  The call returns after its stream work is
+ * complete.  The caller folds min_next_wake_ns into the minimum it hands to srg_next_window: a
+ * pending forward task is a local event of its host.
+ *   Outside the call: the interface and sockets behind the relay; relay_inet_out (the upstream
+ * bucket, fed by the interface's socket scheduler); the order between a forward task and another
+ * local event of the same host at the same nanosecond (by event id in the reference; it changes no
+ * output of this call).  With the CPU-delay model on, the caller passes the time at which each
+ * packet event actually ran.                                                                     */
+/* opaque; lives in the HBM of ctx's device; not thread-safe; destroy it before its ctx */
+typedef struct srg_inbound srg_inbound;
+/* bw_down_bits: host array [num_hosts] (srg_graph_node_bandwidth's value of the host's node);
+ * reserve_packets: router-queue capacity allocated up front (growth reallocates geometrically) */
+int srg_inbound_create(srg_ctx* ctx, uint32_t num_hosts, const uint64_t* bw_down_bits, uint64_t sim_start_ns,
+                       uint64_t bootstrap_end_ns, uint64_t reserve_packets, srg_inbound** out, char* errbuf,
+                       size_t errlen);
+void srg_inbound_destroy(srg_inbound* q);
+
+typedef struct srg_inbound_result {
+    uint64_t num_forwarded, num_dropped; /* left the router in this step */
+    uint64_t num_queued;                 /* still in router queues + cached packets, after the step */
+    uint64_t min_next_wake_ns;           /* min pending forward-task time over hosts, UINT64_MAX if none */
+    double ms_total;
+} srg_inbound_result;
+
+/* time_ns_dev, tag_dev, host_offsets_dev[num_hosts + 1]: exactly what srg_event_queues_pop_device
+ * wrote; total_size_dev[num_arrivals]: each packet's total size (packet.total_size()).          */
+int srg_inbound_step_device(srg_inbound* q, uint64_t until_ns, uint64_t num_arrivals, const uint64_t* time_ns_dev,
+                            const uint32_t* total_size_dev, const uint64_t* tag_dev, const uint64_t* host_offsets_dev,
+                            uint64_t out_capacity, uint8_t* out_status_dev, uint64_t* out_time_ns_dev,
+                            uint64_t* out_tag_dev, uint64_t* out_host_offsets_dev, void* hip_stream,
+                            srg_inbound_result* result, char* errbuf, size_t errlen);
+
+/* (a struct tag, not a typedef: the read-back below has the same name) */
+struct srg_inbound_host_state {
+    uint64_t balance, last_refill_ns;       /* TokenBucket (balance 0 on an unlimited host) */
+    uint64_t interval_end_ns, drop_next_ns; /* valid with has_interval_end / has_drop_next */
+    uint64_t current_drop_count, previous_drop_count, bytes_stored;
+    uint64_t queued;                        /* packets in the CoDel queue (the cached one is not) */
+    uint64_t wake_ns, cached_tag;           /* valid with pending / has_cached */
+    uint8_t mode;                           /* 0 Store, 1 Drop */
+    uint8_t has_interval_end, has_drop_next, pending, has_cached, reserved[3];
+};
+/* one small read-back; SRG_ERR_ARG for host >= num_hosts */
+int srg_inbound_host_state(srg_inbound* q, uint32_t host, struct srg_inbound_host_state* out);
+
 /* ---- the routes a table's paths take; per-edge packet loads --------------------------------
  * The reference keeps no routes: petgraph's dijkstra returns scores only (mod.rs:190-208).  They
  * can be read back from a finished shortest-path table alone, because a Dijkstra label is

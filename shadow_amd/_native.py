@@ -167,6 +167,43 @@ class QueueResult(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class InboundResult(ctypes.Structure):
+    _fields_ = [
+        ("num_forwarded", ctypes.c_uint64),
+        ("num_dropped", ctypes.c_uint64),
+        ("num_queued", ctypes.c_uint64),
+        ("min_next_wake_ns", ctypes.c_uint64),
+        ("ms_total", ctypes.c_double),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class InboundHostState(ctypes.Structure):
+    _fields_ = [
+        ("balance", ctypes.c_uint64),
+        ("last_refill_ns", ctypes.c_uint64),
+        ("interval_end_ns", ctypes.c_uint64),
+        ("drop_next_ns", ctypes.c_uint64),
+        ("current_drop_count", ctypes.c_uint64),
+        ("previous_drop_count", ctypes.c_uint64),
+        ("bytes_stored", ctypes.c_uint64),
+        ("queued", ctypes.c_uint64),
+        ("wake_ns", ctypes.c_uint64),
+        ("cached_tag", ctypes.c_uint64),
+        ("mode", ctypes.c_uint8),
+        ("has_interval_end", ctypes.c_uint8),
+        ("has_drop_next", ctypes.c_uint8),
+        ("pending", ctypes.c_uint8),
+        ("has_cached", ctypes.c_uint8),
+        ("reserved", ctypes.c_uint8 * 3),
+    ]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "reserved"}
+
+
 class RouteResult(ctypes.Structure):
     _fields_ = [
         ("num_pairs", ctypes.c_uint64),
@@ -237,6 +274,7 @@ EXPORTS = [
     "srg_event_queues_create", "srg_event_queues_destroy", "srg_event_queues_merge_tile",
     "srg_event_queues_push_device", "srg_event_queues_pop_device", "srg_next_window",
     "srg_trace_routes_device", "srg_link_loads_device", "srg_route_trees_device", "srg_link_loads_trees_device",
+    "srg_inbound_create", "srg_inbound_destroy", "srg_inbound_step_device", "srg_inbound_host_state",
 ]
 
 _lib = None
@@ -340,6 +378,17 @@ def lib():
     L.srg_event_queues_pop_device.argtypes = [
         c.c_void_p, c.c_uint64, c.c_uint64, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p,
         c.POINTER(QueueResult), c.c_char_p, c.c_size_t]
+    L.srg_inbound_create.restype = c.c_int
+    L.srg_inbound_create.argtypes = [c.c_void_p, c.c_uint32, c.c_void_p, c.c_uint64, c.c_uint64, c.c_uint64,
+                                     c.POINTER(c.c_void_p), c.c_char_p, c.c_size_t]
+    L.srg_inbound_destroy.restype = None
+    L.srg_inbound_destroy.argtypes = [c.c_void_p]
+    L.srg_inbound_step_device.restype = c.c_int
+    L.srg_inbound_step_device.argtypes = [
+        c.c_void_p, c.c_uint64, c.c_uint64, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_uint64, c.c_void_p,
+        c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.POINTER(InboundResult), c.c_char_p, c.c_size_t]
+    L.srg_inbound_host_state.restype = c.c_int
+    L.srg_inbound_host_state.argtypes = [c.c_void_p, c.c_uint32, c.POINTER(InboundHostState)]
     L.srg_next_window.restype = c.c_int
     L.srg_next_window.argtypes = [c.c_uint64, c.c_uint64, c.c_uint64, _u64p, _u64p]
     L.srg_trace_routes_device.restype = c.c_int

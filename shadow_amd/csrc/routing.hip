@@ -61,6 +61,7 @@
 #include "route_rule.h"
 #include "route_tree_rule.h"
 #include "event_queue.hip.h"
+#include "inbound.hip.h"
 #include "xchg.hip.h"
 
 #include <hipcub/hipcub.hpp>
@@ -2284,6 +2285,7 @@ void direct_device(srg_ctx& c, const DevGraph& g, const uint32_t* nodes, uint32_
 }
 
 #include "events_run.hip.h"
+#include "inbound_run.hip.h"
 #include "h2d_codec.hip.h"
 
 int guard(char* errbuf, size_t errlen, const std::function<void()>& body) {
@@ -3113,6 +3115,95 @@ int srg_event_queues_pop_device(srg_event_queues* q, uint64_t until_ns, uint64_t
         evq_pop(*q, until_ns, out_capacity, out_time, out_src, out_id, out_tag, out_off, st, res);
     });
 }
+
+int srg_inbound_create(srg_ctx* ctx, uint32_t num_hosts, const uint64_t* bw_down_bits, uint64_t sim_start_ns,
+                       uint64_t bootstrap_end_ns, uint64_t reserve_packets, srg_inbound** out, char* errbuf,
+                       size_t errlen) {
+    if (!ctx || !out || (num_hosts && !bw_down_bits)) {
+        set_err(errbuf, errlen, "null argument");
+        return SRG_ERR_ARG;
+    }
+    *out = nullptr;
+    if (sim_start_ns >= INB_TIME_END) {
+        set_err(errbuf, errlen, "sim_start_ns outside the time domain (>= 2^62)");
+        return SRG_ERR_ARG;
+    }
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    return guard(errbuf, errlen, [&]() {
+        HIP_CHECK(hipSetDevice(ctx->device));
+        std::unique_ptr<srg_inbound> q(new srg_inbound);
+        q->ctx = ctx;
+        q->num_hosts = num_hosts;
+        q->sim_start = sim_start_ns;
+        q->bootstrap_end = bootstrap_end_ns;
+        const size_t hb = ((size_t)num_hosts + 1) * 8;
+        for (auto& s : q->set) {
+            HIP_CHECK(hipMemsetAsync(s.host_off.get(hb), 0, hb, ctx->stream));
+            s.hosts.get((size_t)num_hosts * sizeof(InbHost));
+            s.reserve(reserve_packets);
+        }
+        for (DevBuf* b : {&q->cnt, &q->rem, &q->offs}) b->get(hb);
+        q->hout.get((size_t)num_hosts * sizeof(InbHostOut));
+        q->red.get(sizeof(InbReduce));
+        uint64_t* inc = (uint64_t*)q->inc.get((size_t)num_hosts * 8);
+        if (num_hosts) {
+            uint64_t* bw = (uint64_t*)q->scr_time.get((size_t)num_hosts * 8);
+            HIP_CHECK(hipMemcpyAsync(bw, bw_down_bits, (size_t)num_hosts * 8, hipMemcpyHostToDevice, ctx->stream));
+            k_inb_init<<<grid_for(num_hosts), kThreads, 0, ctx->stream>>>(bw, num_hosts, sim_start_ns, inc,
+                                                                          (InbHost*)q->set[0].hosts.p,
+                                                                          (InbHost*)q->set[1].hosts.p);
+            HIP_CHECK(hipGetLastError());
+        }
+        HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        *out = q.release();
+    });
+}
+
+void srg_inbound_destroy(srg_inbound* q) {
+    if (!q) return;
+    {
+        std::lock_guard<std::mutex> lk(q->ctx->mu);
+        (void)hipSetDevice(q->ctx->device);
+    }
+    delete q;
+}
+
+int srg_inbound_step_device(srg_inbound* q, uint64_t until_ns, uint64_t num_arrivals, const uint64_t* time_ns,
+                            const uint32_t* total_size, const uint64_t* tag, const uint64_t* host_offsets,
+                            uint64_t out_capacity, uint8_t* out_status, uint64_t* out_time, uint64_t* out_tag,
+                            uint64_t* out_off, void* hip_stream, srg_inbound_result* res, char* errbuf, size_t errlen) {
+    if (!q || !host_offsets || (num_arrivals && (!time_ns || !total_size || !tag)) ||
+        (out_capacity && (!out_status || !out_time || !out_tag || !out_off))) {
+        set_err(errbuf, errlen, "null argument");
+        return SRG_ERR_ARG;
+    }
+    return device_call(q->ctx, hip_stream, res ? &res->ms_total : nullptr, errbuf, errlen, [&](hipStream_t st) {
+        inb_step(*q, until_ns, InbArrivals{num_arrivals, time_ns, total_size, tag, host_offsets}, out_capacity,
+                 out_status, out_time, out_tag, out_off, st, res);
+    });
+}
+
+int srg_inbound_host_state(srg_inbound* q, uint32_t host, struct srg_inbound_host_state* out) {
+    if (!q || !out) return SRG_ERR_ARG;
+    return device_call(q->ctx, nullptr, nullptr, nullptr, 0, [&](hipStream_t) { inb_host_state(*q, host, out); });
+}
+
+#ifdef SRG_TEST_HOOKS
+// TEST HOOK (test build only, not in the header): the device's control-law increments for counts[n]
+int srg_test_inbound_control_law(srg_ctx* ctx, const uint64_t* counts, uint32_t n, uint64_t* out) {
+    if (!ctx || !counts || !out || !n) return SRG_ERR_ARG;
+    return device_call(ctx, nullptr, nullptr, nullptr, 0, [&](hipStream_t st) {
+        DevBuf in, res;
+        in.get((size_t)n * 8);
+        res.get((size_t)n * 8);
+        HIP_CHECK(hipMemcpyAsync(in.p, counts, (size_t)n * 8, hipMemcpyHostToDevice, st));
+        k_inb_test_law<<<grid_for(n), kThreads, 0, st>>>((const uint64_t*)in.p, n, (uint64_t*)res.p);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpyAsync(out, res.p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+    });
+}
+#endif
 
 int srg_trace_routes_device(srg_ctx* ctx, const srg_edge_list* g, const srg_path_table_dev* t, const uint32_t* src,
                             const uint32_t* dst, uint64_t num_pairs, uint64_t hop_capacity, uint64_t* out_off,

@@ -353,3 +353,85 @@ class EventQueues:
         sres = send_packets_device(self.router, dbatch, table, status, deliver, order, off, counts)
         qres = self.push(dbatch, deliver, order, sres["num_sent"], tags)
         return sres, qres, status
+
+
+class Inbound:
+    """The hosts' inbound path, resident in HBM across steps (srg_inbound_*, inbound.hip.h): per host
+    the router's CoDel queue (codel_queue.rs:125-319) and the inbound relay with its token bucket
+    (relay/mod.rs:111-288, token_bucket.rs:68-157).  step() takes what EventQueues.pop returned, plus
+    each packet's total size; the caller folds min_next_wake_ns into the minimum it hands to
+    next_window: a pending forward task is a local event of its host."""
+
+    def __init__(self, router, bw_down_bits, sim_start_ns, bootstrap_end_ns, reserve=0):
+        self.router = router
+        self.dev = torch.device(f"cuda:{router.device}")
+        bw = np.ascontiguousarray(bw_down_bits, dtype=np.uint64)
+        self.num_hosts = int(bw.shape[0])
+        h = ctypes.c_void_p()
+        err = ctypes.create_string_buffer(1024)
+        rc = N.lib().srg_inbound_create(router._h, self.num_hosts, bw.ctypes.data, int(sim_start_ns),
+                                        int(bootstrap_end_ns), int(reserve), ctypes.byref(h), err, len(err))
+        if rc != N.SRG_OK:
+            _raise(rc, err.value.decode(errors="replace"))
+        self._h = h
+        self.num_queued = 0
+        self.min_next_wake_ns = 2**64 - 1
+
+    def close(self):
+        if self._h:
+            N.lib().srg_inbound_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def step_device(self, until_ns, num_arrivals, time_t, size_t, tag_t, host_off_t, capacity, out_status_t, out_time_t,
+                    out_tag_t, out_off_t, stream=None):
+        """Raw call; returns (rc, result dict, message) and raises nothing: a short capacity is
+        SRG_ERR_ARG with num_forwarded + num_dropped = the count needed.  time_t, tag_t, host_off_t
+        int64 and size_t int32 tensors on the device, as EventQueues.pop_device wrote them;
+        outputs uint8 / int64 / int64 [capacity] and int64 [num_hosts + 1]."""
+        res = N.InboundResult()
+        err = ctypes.create_string_buffer(1024)
+        s = stream if stream is not None else torch.cuda.current_stream(self.dev)
+
+        def ptr(t):
+            return t.data_ptr() if t is not None else None
+        rc = N.lib().srg_inbound_step_device(
+            self._h, int(until_ns), int(num_arrivals), ptr(time_t), ptr(size_t), ptr(tag_t), ptr(host_off_t),
+            int(capacity), ptr(out_status_t), ptr(out_time_t), ptr(out_tag_t), ptr(out_off_t),
+            ctypes.c_void_p(s.cuda_stream), ctypes.byref(res), err, len(err))
+        if rc == N.SRG_OK:
+            self.num_queued, self.min_next_wake_ns = int(res.num_queued), int(res.min_next_wake_ns)
+        return rc, res.as_dict(), err.value.decode(errors="replace")
+
+    def step(self, until_ns, time, size, tag, host_offsets):
+        """Device tensors (or host arrays, uploaded) in; returns device tensors (status uint8, time
+        int64, tag int64, host_offsets int64 [H + 1], result).  Sized by num_queued + arrivals,
+        which always suffices."""
+        dev = self.dev
+
+        def dev_t(a, up):
+            return a if isinstance(a, torch.Tensor) else up(np.asarray(a), dev)
+        time_t, size_t, tag_t, off_t = dev_t(time, _i64), dev_t(size, _i32), dev_t(tag, _i64), dev_t(host_offsets, _i64)
+        n = int(time_t.numel())
+        cap = self.num_queued + n
+        status = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
+        otime = torch.empty(max(cap, 1), dtype=torch.int64, device=dev)
+        otag = torch.empty(max(cap, 1), dtype=torch.int64, device=dev)
+        ooff = torch.empty(self.num_hosts + 1, dtype=torch.int64, device=dev)
+        rc, res, msg = self.step_device(until_ns, n, time_t, size_t, tag_t, off_t, max(cap, 1), status, otime, otag, ooff)
+        if rc != N.SRG_OK:
+            _raise_queue(rc, msg)
+        m = res["num_forwarded"] + res["num_dropped"]
+        return status[:m], otime[:m], otag[:m], ooff, res
+
+    def host_state(self, h):
+        out = N.InboundHostState()
+        rc = N.lib().srg_inbound_host_state(self._h, int(h), ctypes.byref(out))
+        if rc != N.SRG_OK:
+            _raise(rc, "srg_inbound_host_state: host out of range")
+        return out.as_dict()
