@@ -583,10 +583,10 @@ int srg_next_window(uint64_t min_next_event_ns, uint64_t runahead_ns, uint64_t e
  * returns an error leaves the state exactly as it was.  The call returns after its stream work is
  * complete.  The caller folds min_next_wake_ns into the minimum it hands to srg_next_window: a
  * pending forward task is a local event of its host.
- *   Outside the call: the interface and sockets behind the relay; relay_inet_out (the upstream
- * bucket, fed by the interface's socket scheduler); the order between a forward task and another
- * local event of the same host at the same nanosecond (by event id in the reference; it changes no
- * output of this call).  With the CPU-delay model on, the caller passes the time at which each
+ *   Outside the call: the interface and sockets behind the relay (relay_inet_out, the upstream
+ * bucket fed by the interface's socket scheduler, is srg_outbound_* below); the order between a
+ * forward task and another local event of the same host at the same nanosecond (by event id in the
+ * reference; it changes no output of this call).  With the CPU-delay model on, the caller passes the time at which each
  * packet event actually ran.                                                                     */
 /* opaque; lives in the HBM of ctx's device; not thread-safe; destroy it before its ctx */
 typedef struct srg_inbound srg_inbound;
@@ -624,6 +624,108 @@ struct srg_inbound_host_state {
 };
 /* one small read-back; SRG_ERR_ARG for host >= num_hosts */
 int srg_inbound_host_state(srg_inbound* q, uint32_t host, struct srg_inbound_host_state* out);
+
+/* ---- the hosts' outbound path: socket qdisc, upstream token bucket ---------------------------
+ * What lies between a socket that has a packet and Worker::send_packet:
+ *   notify_socket_has_packets(socket)     -> networkinterface_wantsSend, relay_inet_out.notify(host)
+ *                                              host.rs:1003-1017, network_interface.c:344-370
+ *   forward task -> forward_until_blocked: networkinterface_pop (the qdisc picks a socket, the socket
+ *       gives its next packet), TokenBucket::comforming_remove(total_size), Router::push =
+ *       Worker::send_packet          relay/mod.rs:166-273, network_interface.c:205-340, router/mod.rs:49-77
+ * kept per host in HBM across steps: the sockets' packets (a socket is a slot; priority 0 is a
+ * control packet and goes into the slot's control FIFO, any other priority into its data FIFO; the
+ * slot's next packet is the control FIFO's head, else the data FIFO's: socket.c:198-199,437-442),
+ * the qdisc structure, the bucket (refill max(1, bw_up_bits / 8 / 1000) per 1 ms, capacity refill +
+ * 1500, created full; bw_up_bits == UINT64_MAX is RateLimit::Unlimited) and the relay (Idle /
+ * Pending, one cached packet).
+ *   SRG_QDISC_FIFO: the reference's binary heap of sockets, restated literally
+ *       (utility/priority_queue.c:87-175, network_queuing_disciplines.c:82-160).  The heap stores no
+ *       keys: a compare reads the two sockets' current next-packet priority, `a` is smaller than `b`
+ *       unless prio(a) > prio(b) (equal keys compare as smaller both ways), an offer to a socket that
+ *       is already in the heap re-sifts nothing (a control packet offered there leaves a stale
+ *       position), pop moves the last entry to the root and sifts it down, preferring the right
+ *       child only when it compares smaller than the left.  Equal non-zero priorities are accepted
+ *       and ordered as this heap orders them.  It is not "the smallest queued priority".
+ *   SRG_QDISC_ROUND_ROBIN: a plain queue of sockets; pop the head, pull its next packet, push it to
+ *       the tail if it has more (network_interface.c:205-247).
+ *   An offer (one packet entering slot `socket` at time_ns): a slot not in the structure is pushed
+ *   into it; if the relay is Idle a forward task is scheduled at the offer's time.  The task at T
+ *   loops: the cached packet, else the qdisc's selection step; none: Idle.  At T >= bootstrap_end_ns
+ *   a packet without SRG_OFFER_LOCAL on a limited host removes total_size tokens; on failure the
+ *   packet is cached and the task runs again at T + the conforming duration.  Otherwise the packet
+ *   leaves at T: status 1, sent to the router -- out_time_ns is its srg_send_batch.send_time_ns --
+ *   or status 2, a local packet (its destination is the host's own address: pushed back into the
+ *   interface, no tokens, but it waits behind a cached packet like any other).
+ *   Order of offers and tasks: in the reference a forward task is a local event, ordered by event id
+ *   among its host's other local events of the same nanosecond; only the caller knows those ids, so
+ *   an offer says it with one bit.  A host's offers are given in execution order with non-decreasing
+ *   times.  Before offer i at time t is enqueued, every pending task with wake < t runs; a pending
+ *   task with wake == t runs first if and only if the offer carries SRG_OFFER_BARRIER -- without the
+ *   bit it runs after this offer and the following offers at t, up to the next barrier offer.  After
+ *   the last offer every task with time < until_ns runs; a task at exactly until_ns stays pending.
+ *   Without any barrier this is the inbound rule.  With the FIFO qdisc, unique increasing priorities
+ *   and no control packets the bit changes no output; with control packets, or round robin, it does.
+ *   Domain: sim_start_ns <= every time < 2^62, until_ns <= 2^62; outside it, offsets that are not
+ *        monotone from 0 to num_offers, a time >= until_ns, a slot >= sockets_per_host[h], an unknown
+ *        flag bit, a qdisc other than 0 or 1: SRG_ERR_ARG
+ *   a packet without SRG_OFFER_LOCAL larger than a limited host's bucket capacity: SRG_ERR_ARG (a
+ *        deviation shared with the inbound call: the balance is clamped to the capacity, so the
+ *        reference's relay would reschedule itself every refill for ever)
+ *   an offer earlier than its host's previous offer or its last executed task: SRG_ERR_TIME_BACKWARD
+ * Outputs are grouped by host (increasing HostId), each host's packets in the order they left: the
+ * order of the host's send_packet calls, so the order in which the caller draws `chance` and event
+ * ids.  With out_capacity 0 every output may be NULL; more packets leaving than out_capacity:
+ * SRG_ERR_ARG, num_sent + num_local = the count needed, nothing changed; (num_queued before the
+ * call) + num_offers always suffices.  Any call that returns an error leaves the state exactly as it
+ * was.  The call returns after its stream work is complete.  The caller folds min_next_wake_ns into
+ * the minimum it hands to srg_next_window.
+ *   Outside the call: the socket-buffer feedback to the process (the space a pulled packet frees),
+ * relay_loopback, pcap and tracker side effects.                                                 */
+#define SRG_QDISC_FIFO 0
+#define SRG_QDISC_ROUND_ROBIN 1
+#define SRG_OFFER_LOCAL 1u   /* dst is the host's own address: no tokens, status 2 */
+#define SRG_OFFER_BARRIER 2u /* a forward task due at this offer's time runs before it */
+/* opaque; lives in the HBM of ctx's device; not thread-safe; destroy it before its ctx */
+typedef struct srg_outbound srg_outbound;
+/* bw_up_bits, sockets_per_host: host arrays [num_hosts] (srg_graph_node_bandwidths' host_bandwidth_up
+ * of the host's node; the number of socket slots of the host, below 2^31); reserve_packets: socket
+ * capacity allocated up front (growth reallocates geometrically) */
+int srg_outbound_create(srg_ctx* ctx, uint32_t num_hosts, const uint64_t* bw_up_bits, const uint32_t* sockets_per_host,
+                        int qdisc, uint64_t sim_start_ns, uint64_t bootstrap_end_ns, uint64_t reserve_packets,
+                        srg_outbound** out, char* errbuf, size_t errlen);
+void srg_outbound_destroy(srg_outbound* q);
+
+typedef struct srg_outbound_result {
+    uint64_t num_sent, num_local; /* left in this step: to the router / back into the interface */
+    uint64_t num_queued;          /* still in sockets + cached packets, after the step */
+    uint64_t min_next_wake_ns;    /* min pending forward-task time over hosts, UINT64_MAX if none */
+    double ms_total;
+} srg_outbound_result;
+
+/* The offers, grouped by host (host_offsets_dev[num_hosts + 1]), each host's in execution order:
+ * time_ns_dev, socket_dev (slot < sockets_per_host[h]), priority_dev (0: control), total_size_dev,
+ * flags_dev (SRG_OFFER_*; NULL = all 0), tag_dev (the caller's handle, returned in out_tag_dev).
+ * out_status_dev: 1 sent to the router, 2 local.                                                */
+int srg_outbound_step_device(srg_outbound* q, uint64_t until_ns, uint64_t num_offers, const uint64_t* time_ns_dev,
+                             const uint32_t* socket_dev, const uint64_t* priority_dev, const uint32_t* total_size_dev,
+                             const uint8_t* flags_dev, const uint64_t* tag_dev, const uint64_t* host_offsets_dev,
+                             uint64_t out_capacity, uint8_t* out_status_dev, uint64_t* out_time_ns_dev,
+                             uint64_t* out_tag_dev, uint64_t* out_host_offsets_dev, void* hip_stream,
+                             srg_outbound_result* result, char* errbuf, size_t errlen);
+
+/* (a struct tag, not a typedef: the read-back below has the same name) */
+struct srg_outbound_host_state {
+    uint64_t balance, last_refill_ns; /* TokenBucket (balance 0 on an unlimited host) */
+    uint64_t wake_ns, cached_tag;     /* valid with pending / has_cached */
+    uint64_t queued;                  /* packets in the host's sockets (the cached one is not) */
+    uint32_t qdisc_len;               /* sockets in the heap / the round-robin queue */
+    uint8_t pending, has_cached, reserved[2];
+};
+/* one small read-back; SRG_ERR_ARG for host >= num_hosts */
+int srg_outbound_host_state(srg_outbound* q, uint32_t host, struct srg_outbound_host_state* out);
+/* the heap array (or the round-robin queue from its head) in array order: *n slots, the first
+ * min(*n, capacity) of them in slots[]; SRG_ERR_ARG for host >= num_hosts */
+int srg_outbound_host_order(srg_outbound* q, uint32_t host, uint32_t* slots, uint32_t capacity, uint32_t* n);
 
 /* ---- the routes a table's paths take; per-edge packet loads --------------------------------
  * The reference keeps no routes: petgraph's dijkstra returns scores only (mod.rs:190-208).  They

@@ -204,6 +204,36 @@ class InboundHostState(ctypes.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "reserved"}
 
 
+class OutboundResult(ctypes.Structure):
+    _fields_ = [
+        ("num_sent", ctypes.c_uint64),
+        ("num_local", ctypes.c_uint64),
+        ("num_queued", ctypes.c_uint64),
+        ("min_next_wake_ns", ctypes.c_uint64),
+        ("ms_total", ctypes.c_double),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class OutboundHostState(ctypes.Structure):
+    _fields_ = [
+        ("balance", ctypes.c_uint64),
+        ("last_refill_ns", ctypes.c_uint64),
+        ("wake_ns", ctypes.c_uint64),
+        ("cached_tag", ctypes.c_uint64),
+        ("queued", ctypes.c_uint64),
+        ("qdisc_len", ctypes.c_uint32),
+        ("pending", ctypes.c_uint8),
+        ("has_cached", ctypes.c_uint8),
+        ("reserved", ctypes.c_uint8 * 2),
+    ]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "reserved"}
+
+
 class RouteResult(ctypes.Structure):
     _fields_ = [
         ("num_pairs", ctypes.c_uint64),
@@ -275,6 +305,8 @@ EXPORTS = [
     "srg_event_queues_push_device", "srg_event_queues_pop_device", "srg_next_window",
     "srg_trace_routes_device", "srg_link_loads_device", "srg_route_trees_device", "srg_link_loads_trees_device",
     "srg_inbound_create", "srg_inbound_destroy", "srg_inbound_step_device", "srg_inbound_host_state",
+    "srg_outbound_create", "srg_outbound_destroy", "srg_outbound_step_device", "srg_outbound_host_state",
+    "srg_outbound_host_order",
 ]
 
 _lib = None
@@ -389,6 +421,20 @@ def lib():
         c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.POINTER(InboundResult), c.c_char_p, c.c_size_t]
     L.srg_inbound_host_state.restype = c.c_int
     L.srg_inbound_host_state.argtypes = [c.c_void_p, c.c_uint32, c.POINTER(InboundHostState)]
+    L.srg_outbound_create.restype = c.c_int
+    L.srg_outbound_create.argtypes = [c.c_void_p, c.c_uint32, c.c_void_p, c.c_void_p, c.c_int, c.c_uint64, c.c_uint64,
+                                      c.c_uint64, c.POINTER(c.c_void_p), c.c_char_p, c.c_size_t]
+    L.srg_outbound_destroy.restype = None
+    L.srg_outbound_destroy.argtypes = [c.c_void_p]
+    L.srg_outbound_step_device.restype = c.c_int
+    L.srg_outbound_step_device.argtypes = [
+        c.c_void_p, c.c_uint64, c.c_uint64, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p,
+        c.c_void_p, c.c_uint64, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.POINTER(OutboundResult),
+        c.c_char_p, c.c_size_t]
+    L.srg_outbound_host_state.restype = c.c_int
+    L.srg_outbound_host_state.argtypes = [c.c_void_p, c.c_uint32, c.POINTER(OutboundHostState)]
+    L.srg_outbound_host_order.restype = c.c_int
+    L.srg_outbound_host_order.argtypes = [c.c_void_p, c.c_uint32, c.c_void_p, c.c_uint32, c.POINTER(c.c_uint32)]
     L.srg_next_window.restype = c.c_int
     L.srg_next_window.argtypes = [c.c_uint64, c.c_uint64, c.c_uint64, _u64p, _u64p]
     L.srg_trace_routes_device.restype = c.c_int

@@ -15,7 +15,9 @@
 // sparse, sparse_ds, events, event_queue, xchg); routes.hip.h (route tracing and link loads over a
 // finished table, rule in route_rule.h) and route_trees.hip.h (whole route trees and loads pushed
 // up them, rules in route_tree_rule.h), sections too; events_run.hip.h (the packet-event batch and
-// event-queue drivers), a section; h2d_codec.hip.h (the host entry's plain copy, H2D codec and
+// event-queue drivers), inbound_run.hip.h and outbound_run.hip.h (the hosts' inbound and outbound
+// paths: kernels in inbound.hip.h / outbound.hip.h, rules in inbound_rule.h / outbound_rule.h),
+// sections; h2d_codec.hip.h (the host entry's plain copy, H2D codec and
 // late-loss thread) and host_entry.hip.h (the host entry, stage by stage), the last two sections.
 // Still here, in order: the validation / W / certify / extract kernels, the context (srg_ctx),
 // prelude(), HostSink, the FW schedules (stream_hop, fw_blocked, SymFw, FwOverlap),
@@ -62,6 +64,7 @@
 #include "route_tree_rule.h"
 #include "event_queue.hip.h"
 #include "inbound.hip.h"
+#include "outbound.hip.h"
 #include "xchg.hip.h"
 
 #include <hipcub/hipcub.hpp>
@@ -2286,6 +2289,7 @@ void direct_device(srg_ctx& c, const DevGraph& g, const uint32_t* nodes, uint32_
 
 #include "events_run.hip.h"
 #include "inbound_run.hip.h"
+#include "outbound_run.hip.h"
 #include "h2d_codec.hip.h"
 
 int guard(char* errbuf, size_t errlen, const std::function<void()>& body) {
@@ -3186,6 +3190,100 @@ int srg_inbound_step_device(srg_inbound* q, uint64_t until_ns, uint64_t num_arri
 int srg_inbound_host_state(srg_inbound* q, uint32_t host, struct srg_inbound_host_state* out) {
     if (!q || !out) return SRG_ERR_ARG;
     return device_call(q->ctx, nullptr, nullptr, nullptr, 0, [&](hipStream_t) { inb_host_state(*q, host, out); });
+}
+
+int srg_outbound_create(srg_ctx* ctx, uint32_t num_hosts, const uint64_t* bw_up_bits, const uint32_t* sockets_per_host,
+                        int qdisc, uint64_t sim_start_ns, uint64_t bootstrap_end_ns, uint64_t reserve_packets,
+                        srg_outbound** out, char* errbuf, size_t errlen) {
+    if (!ctx || !out || (num_hosts && (!bw_up_bits || !sockets_per_host))) {
+        set_err(errbuf, errlen, "null argument");
+        return SRG_ERR_ARG;
+    }
+    *out = nullptr;
+    if (sim_start_ns >= INB_TIME_END) {
+        set_err(errbuf, errlen, "sim_start_ns outside the time domain (>= 2^62)");
+        return SRG_ERR_ARG;
+    }
+    if (qdisc != SRG_QDISC_FIFO && qdisc != SRG_QDISC_ROUND_ROBIN) {
+        set_err(errbuf, errlen, "qdisc is neither SRG_QDISC_FIFO nor SRG_QDISC_ROUND_ROBIN");
+        return SRG_ERR_ARG;
+    }
+    for (uint32_t h = 0; h < num_hosts; ++h)
+        if (sockets_per_host[h] >= (1u << 31)) {
+            set_err(errbuf, errlen, "sockets_per_host outside the domain (>= 2^31)");
+            return SRG_ERR_ARG;
+        }
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    return guard(errbuf, errlen, [&]() {
+        HIP_CHECK(hipSetDevice(ctx->device));
+        std::unique_ptr<srg_outbound> q(new srg_outbound);
+        q->ctx = ctx;
+        q->num_hosts = num_hosts;
+        q->qdisc = qdisc;
+        q->sim_start = sim_start_ns;
+        q->bootstrap_end = bootstrap_end_ns;
+        q->seg_off_host.assign((size_t)num_hosts + 1, 0);
+        for (uint32_t h = 0; h < num_hosts; ++h) q->seg_off_host[h + 1] = q->seg_off_host[h] + sockets_per_host[h];
+        const uint64_t slots = q->seg_off_host[num_hosts];
+        const size_t hb = ((size_t)num_hosts + 1) * 8;
+        for (auto& s : q->set) {
+            HIP_CHECK(hipMemsetAsync(s.host_off.get(hb), 0, hb, ctx->stream));
+            s.hosts.get((size_t)num_hosts * sizeof(OutHost));
+            for (DevBuf* b : {&s.ord, &s.ch, &s.ct, &s.dh, &s.dt}) b->get(slots * 4);
+            s.nprio.get(slots * 8);
+            s.reserve(reserve_packets);
+        }
+        for (DevBuf* b : {&q->cnt, &q->rem, &q->offs}) b->get(hb);
+        q->red.get(sizeof(OutReduce));
+        HIP_CHECK(hipMemcpyAsync(q->seg_off.get(hb), q->seg_off_host.data(), hb, hipMemcpyHostToDevice, ctx->stream));
+        uint64_t* inc = (uint64_t*)q->inc.get((size_t)num_hosts * 8);
+        if (num_hosts) {
+            uint64_t* bw = (uint64_t*)q->o_time.get((size_t)num_hosts * 8);
+            HIP_CHECK(hipMemcpyAsync(bw, bw_up_bits, (size_t)num_hosts * 8, hipMemcpyHostToDevice, ctx->stream));
+            k_out_init<<<grid_for(std::max<uint64_t>(num_hosts, slots)), kThreads, 0, ctx->stream>>>(
+                bw, num_hosts, slots, sim_start_ns, inc, (OutHost*)q->set[0].hosts.p, (OutHost*)q->set[1].hosts.p,
+                q->set[0].seg(), q->set[1].seg());
+            HIP_CHECK(hipGetLastError());
+        }
+        HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        *out = q.release();
+    });
+}
+
+void srg_outbound_destroy(srg_outbound* q) {
+    if (!q) return;
+    {
+        std::lock_guard<std::mutex> lk(q->ctx->mu);
+        (void)hipSetDevice(q->ctx->device);
+    }
+    delete q;
+}
+
+int srg_outbound_step_device(srg_outbound* q, uint64_t until_ns, uint64_t num_offers, const uint64_t* time_ns,
+                             const uint32_t* socket, const uint64_t* priority, const uint32_t* total_size,
+                             const uint8_t* flags, const uint64_t* tag, const uint64_t* host_offsets, uint64_t out_capacity,
+                             uint8_t* out_status, uint64_t* out_time, uint64_t* out_tag, uint64_t* out_off, void* hip_stream,
+                             srg_outbound_result* res, char* errbuf, size_t errlen) {
+    if (!q || !host_offsets || (num_offers && (!time_ns || !socket || !priority || !total_size || !tag)) ||
+        (out_capacity && (!out_status || !out_time || !out_tag || !out_off))) {
+        set_err(errbuf, errlen, "null argument");
+        return SRG_ERR_ARG;
+    }
+    return device_call(q->ctx, hip_stream, res ? &res->ms_total : nullptr, errbuf, errlen, [&](hipStream_t st) {
+        out_step(*q, until_ns, OutOffers{num_offers, time_ns, socket, priority, total_size, flags, tag, host_offsets},
+                 out_capacity, out_status, out_time, out_tag, out_off, st, res);
+    });
+}
+
+int srg_outbound_host_state(srg_outbound* q, uint32_t host, struct srg_outbound_host_state* out) {
+    if (!q || !out) return SRG_ERR_ARG;
+    return device_call(q->ctx, nullptr, nullptr, nullptr, 0, [&](hipStream_t) { out_host_state(*q, host, out); });
+}
+
+int srg_outbound_host_order(srg_outbound* q, uint32_t host, uint32_t* slots, uint32_t capacity, uint32_t* n) {
+    if (!q || !n || (capacity && !slots)) return SRG_ERR_ARG;
+    return device_call(q->ctx, nullptr, nullptr, nullptr, 0,
+                       [&](hipStream_t) { out_host_order(*q, host, slots, capacity, n); });
 }
 
 #ifdef SRG_TEST_HOOKS

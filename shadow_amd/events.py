@@ -435,3 +435,110 @@ class Inbound:
         if rc != N.SRG_OK:
             _raise(rc, "srg_inbound_host_state: host out of range")
         return out.as_dict()
+
+
+class Outbound:
+    """The hosts' outbound path, resident in HBM across steps (srg_outbound_*, outbound.hip.h): per
+    host the sockets' control and data FIFOs, the interface's qdisc structure (the reference's socket
+    heap restated literally, or the round-robin queue: network_interface.c:205-294,
+    utility/priority_queue.c:87-175) and relay_inet_out with its token bucket (relay/mod.rs:111-288).
+    step() takes the offers of a window (one per packet a socket hands to the interface, in each
+    host's execution order) and returns what left: status 1 packets go to send_packets_device with
+    the returned time as their send_time_ns.  The caller folds min_next_wake_ns into the minimum it
+    hands to next_window: a pending forward task is a local event of its host."""
+
+    def __init__(self, router, bw_up_bits, sockets_per_host, qdisc, sim_start_ns, bootstrap_end_ns, reserve=0):
+        self.router = router
+        self.dev = torch.device(f"cuda:{router.device}")
+        bw = np.ascontiguousarray(bw_up_bits, dtype=np.uint64)
+        ns = np.ascontiguousarray(sockets_per_host, dtype=np.uint32)
+        if bw.shape != ns.shape:
+            _raise(N.SRG_ERR_ARG, "bw_up_bits and sockets_per_host differ in length")
+        self.num_hosts = int(bw.shape[0])
+        self.sockets_per_host = ns
+        h = ctypes.c_void_p()
+        err = ctypes.create_string_buffer(1024)
+        rc = N.lib().srg_outbound_create(router._h, self.num_hosts, bw.ctypes.data, ns.ctypes.data, int(qdisc),
+                                         int(sim_start_ns), int(bootstrap_end_ns), int(reserve), ctypes.byref(h), err,
+                                         len(err))
+        if rc != N.SRG_OK:
+            _raise(rc, err.value.decode(errors="replace"))
+        self._h = h
+        self.num_queued = 0
+        self.min_next_wake_ns = 2**64 - 1
+
+    def close(self):
+        if self._h:
+            N.lib().srg_outbound_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def step_device(self, until_ns, num_offers, time_t, socket_t, priority_t, size_t, flags_t, tag_t, host_off_t, capacity,
+                    out_status_t, out_time_t, out_tag_t, out_off_t, stream=None):
+        """Raw call; returns (rc, result dict, message) and raises nothing: a short capacity is
+        SRG_ERR_ARG with num_sent + num_local = the count needed.  time_t, priority_t, tag_t,
+        host_off_t int64, socket_t, size_t int32 and flags_t uint8 (or None) tensors on the device;
+        outputs uint8 / int64 / int64 [capacity] and int64 [num_hosts + 1]."""
+        res = N.OutboundResult()
+        err = ctypes.create_string_buffer(1024)
+        s = stream if stream is not None else torch.cuda.current_stream(self.dev)
+
+        def ptr(t):
+            return t.data_ptr() if t is not None else None
+        rc = N.lib().srg_outbound_step_device(
+            self._h, int(until_ns), int(num_offers), ptr(time_t), ptr(socket_t), ptr(priority_t), ptr(size_t), ptr(flags_t),
+            ptr(tag_t), ptr(host_off_t), int(capacity), ptr(out_status_t), ptr(out_time_t), ptr(out_tag_t), ptr(out_off_t),
+            ctypes.c_void_p(s.cuda_stream), ctypes.byref(res), err, len(err))
+        if rc == N.SRG_OK:
+            self.num_queued, self.min_next_wake_ns = int(res.num_queued), int(res.min_next_wake_ns)
+        return rc, res.as_dict(), err.value.decode(errors="replace")
+
+    def step(self, until_ns, time, socket, priority, size, flags, tag, host_offsets):
+        """Device tensors (or host arrays, uploaded) in; returns device tensors (status uint8, time
+        int64, tag int64, host_offsets int64 [H + 1], result).  Sized by num_queued + offers, which
+        always suffices."""
+        dev = self.dev
+
+        def dev_t(a, up):
+            return a if isinstance(a, torch.Tensor) or a is None else up(np.asarray(a), dev)
+
+        def _u8(a, d):
+            return torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint8)).to(d)
+        time_t, sock_t, prio_t, size_t = dev_t(time, _i64), dev_t(socket, _i32), dev_t(priority, _i64), dev_t(size, _i32)
+        flags_t, tag_t, off_t = dev_t(flags, _u8), dev_t(tag, _i64), dev_t(host_offsets, _i64)
+        n = int(time_t.numel())
+        cap = max(self.num_queued + n, 1)
+        status = torch.empty(cap, dtype=torch.uint8, device=dev)
+        otime = torch.empty(cap, dtype=torch.int64, device=dev)
+        otag = torch.empty(cap, dtype=torch.int64, device=dev)
+        ooff = torch.empty(self.num_hosts + 1, dtype=torch.int64, device=dev)
+        rc, res, msg = self.step_device(until_ns, n, time_t, sock_t, prio_t, size_t, flags_t, tag_t, off_t, cap, status,
+                                        otime, otag, ooff)
+        if rc != N.SRG_OK:
+            _raise_queue(rc, msg)
+        m = res["num_sent"] + res["num_local"]
+        return status[:m], otime[:m], otag[:m], ooff, res
+
+    def host_state(self, h):
+        out = N.OutboundHostState()
+        rc = N.lib().srg_outbound_host_state(self._h, int(h), ctypes.byref(out))
+        if rc != N.SRG_OK:
+            _raise(rc, "srg_outbound_host_state: host out of range")
+        return out.as_dict()
+
+    def host_order(self, h):
+        """The host's heap array (or round-robin queue from its head) as a list of slots."""
+        if not 0 <= int(h) < self.num_hosts:
+            _raise(N.SRG_ERR_ARG, "srg_outbound_host_order: host out of range")
+        cap = max(int(self.sockets_per_host[int(h)]), 1)
+        buf = (ctypes.c_uint32 * cap)()
+        n = ctypes.c_uint32()
+        rc = N.lib().srg_outbound_host_order(self._h, int(h), buf, cap, ctypes.byref(n))
+        if rc != N.SRG_OK:
+            _raise(rc, "srg_outbound_host_order: host out of range")
+        return [int(buf[i]) for i in range(int(n.value))]
