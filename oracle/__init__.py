@@ -24,10 +24,32 @@ _u64p = ctypes.POINTER(ctypes.c_uint64)
 _f32p = ctypes.POINTER(ctypes.c_float)
 
 
+QDISC_REF = os.path.join(_HERE, "_ref", "qdisc_ref")
+_QDISC_REF_SOURCES = ("main/utility/priority_queue.c", "main/utility/priority_queue.h",
+                      "main/host/network/network_queuing_disciplines.c",
+                      "main/host/network/network_queuing_disciplines.h")
+
+
+def reference_dir():
+    """The reference checkout: $SHADOW_REFERENCE, else a directory `reference` beside the repository."""
+    return os.environ.get("SHADOW_REFERENCE") or os.path.join(os.path.dirname(os.path.dirname(_HERE)), "reference")
+
+
+def build_qdisc_ref():
+    """oracle/_ref/qdisc_ref: the reference's own socket queues (C) compiled in place from a reference
+    checkout against oracle/ref_qdisc/ (ASan + UBSan).  Where the checkout is absent nothing is built
+    and nothing fails: a binary built earlier is used as it is, and the tests need none.  -> path or None."""
+    ref = reference_dir()
+    if all(os.path.exists(os.path.join(ref, "src", f)) for f in _QDISC_REF_SOURCES):
+        subprocess.check_call(["make", "-s", "-C", _HERE, "qdisc_ref", "REFERENCE=" + ref])
+    return QDISC_REF if os.path.exists(QDISC_REF) else None
+
+
 def build():
     src = os.path.join(_HERE, "oracle.cpp")
     if not os.path.exists(_LIB_PATH) or os.path.getmtime(src) > os.path.getmtime(_LIB_PATH):
-        subprocess.check_call(["make", "-s", "-C", _HERE])
+        subprocess.check_call(["make", "-s", "-C", _HERE, "liboracle.so"])
+    build_qdisc_ref()
     return _LIB_PATH
 
 

@@ -13,6 +13,13 @@
 //   relay/mod.rs:111-288                  notify / run_forward_task / forward_until_blocked / create_token_bucket
 //   relay/token_bucket.rs:68-157          the bucket (inbound_rule.h's inb_lazy_refill / inb_conforming_remove)
 //
+// Pinned by the reference's own compiled code: the heap (push, pop, both sifts), its comparator and
+// the round-robin queue.  oracle/_ref/qdisc_ref is priority_queue.c and network_queuing_disciplines.c
+// built from a reference checkout; the scripts it answered are tests/golden/qdisc_reference.json, and
+// this header's leaving order on the qdisc_* scenarios equals that program's selection order
+// (tests/test_outbound_cpu.py).  Still a restatement, here and in that program's driver: the sockets'
+// two FIFOs, wantsSend, the selection loop, the relay and the bucket.
+//
 // The heap is restated literally.  Its keys are not stored: a compare reads the two sockets' current
 // next-packet priority (Q::nprio), so a control packet offered to a socket that already sits in the
 // heap changes that socket's key without a re-sift, and `a` is smaller than `b` unless

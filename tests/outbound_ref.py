@@ -9,6 +9,12 @@ shadow_amd/csrc/outbound_rule.h: its own heap class, deques and event loop.
   network/relay/mod.rs:111-288                        notify, the forward task, create_token_bucket
   network/relay/token_bucket.rs:68-157                TokenBucket (inbound_ref.py's: the same struct)
 
+Pinned by the reference's own compiled code (oracle/_ref/qdisc_ref, built from a checkout by
+oracle/ref_qdisc/; its recorded answers are tests/golden/qdisc_reference.json): SocketHeap with its
+comparator and SocketRing.  Still restated, there as here: Socket's two FIFOs, wantsSend (Host.offer),
+the selection loop (Host.interface_pop), the relay and the bucket.  Host(..., trace=True) records the
+host's offers and selects; trace_script / trace_output give them in that program's format.
+
 The order between an offer and a forward task of the same nanosecond is the caller's (event ids):
 OFFER_BARRIER on an offer says that a task due at the offer's time runs before it.
 COUNTERS counts the branches the tests must reach.
@@ -28,7 +34,8 @@ ERR_TIME_BACKWARD = 12
 BRANCHES = ("bootstrap_forward", "local_exempt", "local_behind_cached", "token_block", "block_multi_refill",
             "offer_at_wake_barrier", "offer_at_wake_no_barrier", "barrier_nothing_pending", "wake_at_window_end",
             "control_before_data", "control_into_queued_socket", "priority0_tie", "right_child_taken",
-            "socket_pushed_back", "socket_leaves", "round_robin_rotation", "unlimited_host")
+            "socket_pushed_back", "socket_leaves", "round_robin_rotation", "unlimited_host",
+            "select_65_queued", "select_129_queued")
 COUNTERS = {k: 0 for k in BRANCHES}
 
 
@@ -153,7 +160,8 @@ class SocketRing:
 class Host:
     """One host's internet interface (sockets + qdisc) and relay_inet_out."""
 
-    def __init__(self, bw_up_bits, num_sockets, qdisc, sim_start, bootstrap_end):
+    def __init__(self, bw_up_bits, num_sockets, qdisc, sim_start, bootstrap_end, trace=False):
+        self.trace = [] if trace else None  # ("o", slot, priority, tag) | ("s", slot, tag) | ("s", None, None)
         self.sockets = [Socket(i) for i in range(num_sockets)]
         self.qdisc = qdisc
         self.q = SocketHeap() if qdisc == QDISC_FIFO else SocketRing()
@@ -166,9 +174,17 @@ class Host:
 
     def interface_pop(self):  # network_interface.c:205-294
         if not len(self.q):
+            if self.trace is not None:
+                self.trace.append(("s", None, None))
             return None
+        if len(self.q) >= 65:
+            hit("select_65_queued")
+        if len(self.q) >= 129:
+            hit("select_129_queued")
         s = self.q.pop()
         pkt = s.pull()
+        if self.trace is not None:
+            self.trace.append(("s", s.slot, pkt[3]))
         if s.has_data():
             hit("socket_pushed_back")
             if self.qdisc == QDISC_ROUND_ROBIN and len(self.q):
@@ -208,6 +224,8 @@ class Host:
             self.out.append((2 if local else 1, now, pkt[3]))
 
     def offer(self, t, slot, pkt):  # host.rs:1003-1017
+        if self.trace is not None:
+            self.trace.append(("o", slot, pkt[0], pkt[3]))
         s = self.sockets[slot]
         in_q = self.q.find(s)
         assert in_q == s.has_data()
@@ -249,11 +267,12 @@ class Host:
 
 
 class Outbound:
-    def __init__(self, bw_up_bits, sockets_per_host, qdisc, sim_start, bootstrap_end):
+    def __init__(self, bw_up_bits, sockets_per_host, qdisc, sim_start, bootstrap_end, trace=False):
         if qdisc not in (QDISC_FIFO, QDISC_ROUND_ROBIN):
             raise OutboundRefError(ERR_ARG, "qdisc")
         self.sim_start = sim_start
-        self.hosts = [Host(int(b), int(n), qdisc, sim_start, bootstrap_end) for b, n in zip(bw_up_bits, sockets_per_host)]
+        self.hosts = [Host(int(b), int(n), qdisc, sim_start, bootstrap_end, trace)
+                      for b, n in zip(bw_up_bits, sockets_per_host)]
 
     def validate(self, until, time, slot, size, flags, offs):
         H, n = len(self.hosts), len(time)
@@ -304,3 +323,34 @@ class Outbound:
 
     def host_order(self, h):
         return self.hosts[h].q.order()
+
+
+# ---- the trace: a host's qdisc operations as a script for oracle/_ref/qdisc_ref ---------------
+def trace_script(qdisc, num_sockets, trace):
+    """A host's trace (Host(..., trace=True).trace) in the reference program's script format:
+    "<qdisc> <sockets>", then "o <slot> <priority> <tag>" per offer and "s" per selection step."""
+    return "".join(["%d %d\n" % (qdisc, num_sockets)] +
+                   ["s\n" if e[0] == "s" else "o %d %d %d\n" % e[1:] for e in trace])
+
+
+def trace_output(trace):
+    """What the reference program prints for that script if it selects as the trace did: "<slot> <tag>"
+    per selection step, "-" for one on an empty qdisc."""
+    return "".join("-\n" if e[1] is None else "%d %d\n" % e[1:] for e in trace if e[0] == "s")
+
+
+def replay_script(text, host_cls=Host):
+    """Runs a script through Socket and SocketHeap / SocketRing (a host with no relay: offer and
+    interface_pop only) -> the output text."""
+    lines = text.splitlines()
+    qdisc, num_sockets = (int(x) for x in lines[0].split())
+    host = host_cls(U64, num_sockets, qdisc, 0, 0, trace=True)
+    for ln in lines[1:]:
+        if ln == "s":
+            host.interface_pop()
+        else:
+            op, slot, prio, tag = ln.split()
+            assert op == "o"
+            host.offer(0, int(slot), (int(prio), 0, 0, int(tag)))
+    assert trace_script(qdisc, num_sockets, host.trace) == text
+    return trace_output(host.trace)

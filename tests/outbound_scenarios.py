@@ -7,6 +7,7 @@ skips them with next_window."""
 import json
 import os
 import random
+import subprocess
 
 import outbound_ref as R
 
@@ -167,6 +168,193 @@ def boundaries(qdisc):
     return ("boundaries_q%d" % qdisc, bw, sockets, qdisc, S, B, steps)
 
 
+# ---- the scenarios whose qdisc operations the reference's own queue code has replayed -----------
+# (tests/golden/qdisc_reference.json holds each host's traced script and that program's output)
+TRICKLE_BW = 7_999  # max(1, 999 // 1000) = 1 token per 1 ms refill, capacity 1501
+
+
+def trickle_offers(seed, t0, sockets, tie, unique, wakes):
+    """One 7 999 bit/s host whose time axis is turned into an arbitrary offer / select interleaving.
+    t0 is a refill boundary at which the bucket is full (nothing removed tokens before).  A 1501 B
+    packet at t0 takes the whole bucket.  At t0 + 0.5 ms every socket gets one packet (the whole heap
+    or ring stands before the next select); from then on the balance is 0 at every refill boundary
+    while packets are queued, so the task at t0 + k ms sends the cached 1 B packet with the refill's
+    one token, selects exactly one more and blocks on it.  Offers lie strictly between the wakes, 1 to
+    3 per ms for 25 ms, then 0 or 1, and so on; a size-0 packet always conforms and a local one needs
+    no tokens, so either gives a second select in the same task; after a quiet stretch that empties
+    the qdisc the idle refills give short runs.  `tie` is the share of priority-0 (control) packets;
+    data priorities are a counter (unique) or drawn from 1..5.  Tags count from 1."""
+    rng = random.Random(seed)
+    out, prio = [(t0, 0, 1, 1501, 0, 1)], 1
+
+    def add(t, slot, size, flags):
+        nonlocal prio
+        prio += 1
+        ctl = rng.random() < tie
+        out.append((t, slot, 0 if ctl else (prio if unique else rng.randrange(1, 6)), size, flags, len(out) + 1))
+
+    slots = list(range(sockets))
+    rng.shuffle(slots)
+    for slot in slots:
+        add(t0 + 500_000, slot, 1, 0)
+    for k in range(1, wakes + 1):
+        n = rng.choice((1, 1, 2, 2, 3)) if (k // 25) % 2 == 0 else rng.choice((0, 0, 0, 1, 1))
+        for j in range(n):
+            add(t0 + k * MS + 200_000 * (j + 1), rng.randrange(sockets), 0 if rng.random() < 0.12 else 1,
+                LOCAL if rng.random() < 0.04 else 0)
+    return out
+
+
+def batch_offers(seed, times, sockets, tie, unique, barrier_in=()):
+    """Batch-then-drain: at each of `times` 1.5 * sockets + 6 offers of 1500 B arrive in one
+    nanosecond (sockets repeat, so a socket holds several packets and control packets enter queued
+    sockets), and where nothing limits the host the one task at that time drains them all.  A batch
+    whose index is in `barrier_in` carries the barrier bit on its middle offer: the task runs there,
+    and the rest of the batch meets an empty qdisc."""
+    rng = random.Random(seed)
+    out, prio = [], 0
+    for b, t in enumerate(times):
+        n = sockets * 3 // 2 + 6
+        for j in range(n):
+            prio += 1
+            ctl = rng.random() < tie
+            out.append((t, rng.randrange(sockets), 0 if ctl else (prio if unique else rng.randrange(1, 6)), 1500,
+                        BARRIER if b in barrier_in and j == n // 2 else 0, len(out) + 1))
+    return out
+
+
+QDISC_TRICKLE_HOSTS = ((1, 0.5, True), (2, 0.1, False), (3, 0.0, True), (7, 0.5, False), (64, 0.1, True),
+                       (65, 0.0, False), (130, 0.1, True))  # (sockets, tie, unique)
+QDISC_BATCH_HOSTS = ((2, 0.5, False), (7, 0.1, True), (65, 0.1, False))
+
+
+def qdisc_trickle_offers(qdisc):
+    """-> (name, qdisc, bw, sockets, bootstrap_end, per-host offers, a time by which everything has left)"""
+    t0 = SIM_START + 3 * MS
+    bw, sockets, offers = [], [], []
+    for i, (n, tie, unique) in enumerate(QDISC_TRICKLE_HOSTS):
+        bw.append(TRICKLE_BW)
+        sockets.append(n)
+        offers.append(trickle_offers(500 + 10 * qdisc + i, t0, n, tie, unique, wakes=100))
+    for i, (n, tie, unique) in enumerate(QDISC_BATCH_HOSTS):
+        bw.append(U64)
+        sockets.append(n)
+        offers.append(batch_offers(600 + 10 * qdisc + i, (t0 + 250_000, t0 + 40 * MS + 1), n, tie, unique, barrier_in=(1,)))
+    return "qdisc_trickle_q%d" % qdisc, qdisc, bw, sockets, SIM_START, offers, t0 + 2_000 * MS
+
+
+def qdisc_bootstrap_offers(qdisc):
+    """Limited hosts before bootstrap_end: two batches drain at once, whatever their size; past it the
+    same hosts trickle."""
+    boot = SIM_START + 20 * MS
+    bw, sockets, offers = [], [], []
+    for i, (n, tie, unique) in enumerate(((3, 0.5, True), (7, 0.1, False), (64, 0.0, True))):
+        bw.append(TRICKLE_BW)
+        sockets.append(n)
+        a = batch_offers(700 + 10 * qdisc + i, (SIM_START + 2 * MS, boot - 1), n, tie, unique, barrier_in=(0,))
+        b = trickle_offers(800 + 10 * qdisc + i, boot + 2 * MS, n, tie, unique, wakes=40)
+        offers.append(a + [(e[0], e[1], e[2], e[3], e[4], len(a) + e[5]) for e in b])
+    return "qdisc_bootstrap_q%d" % qdisc, qdisc, bw, sockets, boot, offers, boot + 1_000 * MS
+
+
+def qdisc_scenario(spec, width=10 * MS):
+    """Windows of `width` while offers arrive (None: everything in one step), then one step to `far`,
+    after which nothing is queued."""
+    name, qdisc, bw, sockets, boot, offers, far = spec
+    nobody = [[] for _ in bw]
+    if width is None:
+        return (name + "_one_step", bw, sockets, qdisc, SIM_START, boot, [(far, offers)])
+    last = max(a[-1][0] for a in offers)
+    end = SIM_START + ((last - SIM_START) // width + 1) * width
+    steps = windowed(bw, sockets, qdisc, boot, offers, width, end) + [(far, nobody)]
+    return (name, bw, sockets, qdisc, SIM_START, boot, steps)
+
+
+def qdisc_specs(qdisc):
+    return [qdisc_trickle_offers(qdisc), qdisc_bootstrap_offers(qdisc)]
+
+
+def qdisc_scenarios():
+    return [qdisc_scenario(spec) for q in (R.QDISC_FIFO, R.QDISC_ROUND_ROBIN) for spec in qdisc_specs(q)]
+
+
+def trace_ref(scn, drained=True):
+    """-> (per-host (script, output) texts in the reference program's format, the reference's outs)"""
+    _, bw, sockets, qdisc, sim_start, boot, steps = scn
+    ref = R.Outbound(bw, sockets, qdisc, sim_start, boot, trace=True)
+    outs = [ref.step(until, *flatten(per_host)) for until, per_host in steps]
+    assert not drained or outs[-1][4]["num_queued"] == 0
+    return [(R.trace_script(qdisc, n, h.trace), R.trace_output(h.trace)) for n, h in zip(sockets, ref.hosts)], outs
+
+
+def free_script(seed, qdisc, sockets, tie, unique):
+    """A free-form script for the reference program: offers and selects interleaved with no time axis.
+    20 ops with offers and selects even, an offer to every socket in a shuffled order (after it every
+    socket is queued), 100 + sockets ops with offers and selects even again, then selects until one
+    finds the qdisc empty."""
+    rng = random.Random(seed)
+    lines, prio, queued = ["%d %d" % (qdisc, sockets)], 0, 0
+
+    def select():
+        nonlocal queued
+        lines.append("s")
+        queued -= queued > 0
+
+    def offer(slot):
+        nonlocal prio, queued
+        prio += 1
+        ctl = rng.random() < tie
+        lines.append("o %d %d %d" % (slot, 0 if ctl else (prio if unique else rng.randrange(1, 6)), prio))
+        queued += 1
+
+    slots = list(range(sockets))
+    rng.shuffle(slots)
+    for phase in (20, None, 100 + sockets):
+        if phase is None:
+            for slot in slots:
+                offer(slot)
+            continue
+        for _ in range(phase):
+            if rng.random() < 0.5:
+                select()
+            else:
+                offer(rng.randrange(sockets))
+    lines += ["s"] * (queued + 1)
+    return "\n".join(lines) + "\n"
+
+
+FREE_SOCKETS = (1, 2, 3, 7, 64, 65, 130)
+FREE_TIES = (0.0, 0.1, 0.5)
+
+
+def free_scripts(seed0, count):
+    """`count` scripts per qdisc: sockets, tie share and priority mode cycle at different periods (7, 3,
+    2), so every value and, from 42 on, every combination occurs."""
+    return [dict(seed=seed0 + k, qdisc=q, sockets=FREE_SOCKETS[k % 7], tie=FREE_TIES[k % 3], unique=k % 2 == 0,
+                 script=free_script(seed0 + k, q, FREE_SOCKETS[k % 7], FREE_TIES[k % 3], k % 2 == 0))
+            for q in (R.QDISC_FIFO, R.QDISC_ROUND_ROBIN) for k in range(count)]
+
+
+def kat_script(k):
+    """A KAT's one host traced over its steps (some end with packets queued) -> (script, output)."""
+    return trace_ref(kat_scenario(k), drained=False)[0][0]
+
+
+def run_qdisc_ref(exe, scripts):
+    """Feeds the scripts to the reference program (oracle/_ref/qdisc_ref) in one process, an "e" line
+    after each -> the output text per script."""
+    r = subprocess.run([exe], input="".join(sc + "e\n" for sc in scripts), capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and r.stderr == "", (r.returncode, r.stderr[-2000:])
+    outs = r.stdout.split("e\n")
+    assert len(outs) == len(scripts) + 1 and outs[-1] == ""
+    return outs[:-1]
+
+
+def load_qdisc_reference():
+    with open(os.path.join(HERE, "golden", "qdisc_reference.json")) as f:
+        return json.load(f)
+
+
 def load_kats():
     with open(os.path.join(HERE, "golden", "outbound_kats.json")) as f:
         return json.load(f)["tests"]
@@ -182,7 +370,7 @@ def all_scenarios():
     for q in (R.QDISC_FIFO, R.QDISC_ROUND_ROBIN):
         out += [overload(None, q), overload(50 * MS, q), overload(1 * MS, q), boundaries(q), shapes(q)]
         out += [chunk_edges(h, q) for h in (1, 3, 64, 65)]
-    return out
+    return out + qdisc_scenarios()
 
 
 def run_ref(scn):

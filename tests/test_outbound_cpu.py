@@ -11,9 +11,20 @@
    is also the "smallest queued priority" model), relevant with control packets and for round robin;
 6. the overload scenario in one step, 50 ms windows and 1 ms windows leaves the same packets at the
    same times;
-7. the new ctypes structs have the C sizes.
+7. the new ctypes structs have the C sizes;
+8. the qdisc against the reference's own compiled code.  tests/golden/qdisc_reference.json holds offer /
+   select scripts with the output of oracle/_ref/qdisc_ref, which is the reference's priority_queue.c
+   and network_queuing_disciplines.c compiled from a checkout (oracle/ref_qdisc/): free interleavings,
+   the operations outbound_ref.py performs on the time-domain scenarios qdisc_* (its trace hook), and
+   those of the KATs.  Where the program is built the fixture regenerates byte for byte and 420 further
+   scripts agree with SocketHeap / SocketRing; without it the fixture replays through those classes,
+   the header's leaving order on the qdisc_* scenarios is the program's selection order, the scripts
+   reach the heap's special cases at 65 and 129 queued sockets, and three plausible wrong heaps each
+   fail on the fixture.  Pinned this way: heap, comparator, round-robin queue.  Still restated (in
+   the driver too): the sockets' FIFOs, wantsSend, the selection loop, relay and bucket.
 The GPU side: tests/test_outbound_gpu.py."""
 import ctypes
+import heapq
 import os
 import shutil
 import subprocess
@@ -193,3 +204,175 @@ def test_struct_sizes():
     assert ctypes.sizeof(N.OutboundResult) == 4 * 8 + 8
     assert ctypes.sizeof(N.OutboundHostState) == 5 * 8 + 4 + 4
     assert N.OutboundHostState.qdisc_len.offset == 40 and N.OutboundHostState.has_cached.offset == 45
+
+
+# ---- 8. the qdisc against the reference's own compiled code -------------------------------------
+QDISC_REF_EXE = os.path.join(os.path.dirname(HERE), "oracle", "_ref", "qdisc_ref")
+FREE_SEED, FREE_COUNT = 1000, 10  # tests/golden/make_qdisc_reference.py
+EXTRA_SEED, EXTRA_COUNT = 50_000, 210  # per qdisc: 5 of every (sockets, tie, priority mode)
+
+
+@pytest.fixture(scope="module")
+def qref():
+    return S.load_qdisc_reference()
+
+
+def fixture_entries(doc):
+    """-> [(id, script, output)]"""
+    out = [("free_%d_q%d" % (e["seed"], e["qdisc"]), e["script"], e["output"]) for e in doc["free"]]
+    for scn in doc["scenarios"]:
+        out += [("%s_host%d" % (scn["name"], h), e["script"], e["output"]) for h, e in enumerate(scn["hosts"])]
+    return out + [("kat_" + e["name"], e["script"], e["output"]) for e in doc["kats"]]
+
+
+def tags_of(output):
+    return [int(ln.split()[1]) for ln in output.splitlines() if ln != "-"]
+
+
+def test_qdisc_fixture_is_what_the_generators_give(qref):
+    """The fixture's scripts are today's: the free scripts of its seeds, the traces of today's
+    scenarios and KATs.  (Their outputs are the reference program's: the regeneration test.)"""
+    assert [e["script"] for e in qref["free"]] == [e["script"] for e in S.free_scripts(FREE_SEED, FREE_COUNT)]
+    scns = S.qdisc_scenarios()
+    assert [x["name"] for x in qref["scenarios"]] == [scn[0] for scn in scns]
+    for x, scn in zip(qref["scenarios"], scns):
+        assert [e["script"] for e in x["hosts"]] == [sc for sc, _ in S.trace_ref(scn)[0]], scn[0]
+    kats = S.load_kats()
+    assert [e["name"] for e in qref["kats"]] == [k["name"] for k in kats]
+    assert [e["script"] for e in qref["kats"]] == [S.kat_script(k)[0] for k in kats]
+    assert os.path.getsize(os.path.join(HERE, "golden", "qdisc_reference.json")) <= \
+        os.path.getsize(os.path.join(HERE, "golden", "routing_vectors.json"))
+
+
+def test_qdisc_reference_program_regenerates_the_fixture(qref):
+    if not os.path.exists(QDISC_REF_EXE):
+        pytest.skip("oracle/_ref/qdisc_ref is not built (no reference checkout)")
+    entries = fixture_entries(qref)
+    got = S.run_qdisc_ref(QDISC_REF_EXE, [sc for _, sc, _ in entries])
+    for (name, _, out), g in zip(entries, got):
+        assert g == out, name
+    extra = S.free_scripts(EXTRA_SEED, EXTRA_COUNT)
+    assert len(extra) >= 400
+    R.reset_counters()
+    got = S.run_qdisc_ref(QDISC_REF_EXE, [e["script"] for e in extra])
+    for e, g in zip(extra, got):
+        assert R.replay_script(e["script"]) == g, (e["seed"], e["qdisc"], e["sockets"], e["tie"], e["unique"])
+    selects = sum(g.count("\n") for g in got)
+    print("qdisc_ref: %d fixture scripts reproduced; %d further scripts, %d selects agree; reached %s"
+          % (len(entries), len(extra), selects, {k: R.COUNTERS[k] for k in QDISC_BRANCHES[0] + QDISC_BRANCHES[1]}))
+    assert selects == sum(e["script"].count("s\n") for e in extra)
+    # every (sockets, tie, priority mode) five times per qdisc: each special case is met many times over
+    assert all(R.COUNTERS[k] >= 100 for k in QDISC_BRANCHES[0] + QDISC_BRANCHES[1][-1:])
+
+
+def test_qdisc_fixture_replays_through_the_restatement(qref):
+    entries = fixture_entries(qref)
+    assert len(entries) == 2 * FREE_COUNT + 26 + 7
+    for name, script, out in entries:
+        assert R.replay_script(script) == out, name
+
+
+QDISC_BRANCHES = {0: ("control_into_queued_socket", "priority0_tie", "right_child_taken", "socket_pushed_back",
+                      "select_65_queued", "select_129_queued"),
+                  1: ("control_into_queued_socket", "socket_pushed_back", "select_65_queued", "select_129_queued",
+                      "round_robin_rotation")}
+
+
+@pytest.mark.parametrize("qdisc", [R.QDISC_FIFO, R.QDISC_ROUND_ROBIN], ids=["fifo", "rr"])
+def test_qdisc_fixture_reaches_the_special_cases(qref, qdisc):
+    """Free scripts and time-domain scenarios (not the KATs), per qdisc, by outbound_ref.py's counters."""
+    R.reset_counters()
+    for e in qref["free"]:
+        if e["qdisc"] == qdisc:
+            R.replay_script(e["script"])
+    for scn in qref["scenarios"]:
+        for e in scn["hosts"]:
+            if int(e["script"].split()[0]) == qdisc:
+                R.replay_script(e["script"])
+    assert all(R.COUNTERS[k] > 0 for k in QDISC_BRANCHES[qdisc]), R.COUNTERS
+    used = {(e["sockets"], e["tie"], e["unique"]) for e in qref["free"] if e["qdisc"] == qdisc}
+    assert {u[0] for u in used} == set(S.FREE_SOCKETS) and {u[1] for u in used} == set(S.FREE_TIES)
+    assert {u[2] for u in used} == {True, False}
+
+
+def test_qdisc_scenarios_leave_every_packet(qref):
+    for x, scn in zip(qref["scenarios"], S.qdisc_scenarios()):
+        traced, outs = S.trace_ref(scn)
+        left = S.concat_by_host(outs, len(scn[1]))
+        for h, e in enumerate(x["hosts"]):
+            offered = [o[5] for _, per_host in scn[6] for o in per_host[h]]
+            assert sorted(g for _, _, g in left[h]) == sorted(offered) and offered, (scn[0], h)
+            assert [g for _, _, g in left[h]] == tags_of(e["output"]), (scn[0], h)
+        assert outs[-1][4]["num_queued"] == 0 and outs[-1][4]["min_next_wake_ns"] == R.U64, scn[0]
+
+
+@pytest.mark.parametrize("scn", S.qdisc_scenarios(), ids=lambda s: s[0])
+def test_header_leaves_in_the_reference_programs_order(rule_check, tmp_path, qref, scn):
+    """The header's leaving packets per host (sent and local), concatenated over the steps, are the
+    packets the reference program selected, in its order.  (That every line equals outbound_ref.py's:
+    test_header_matches_reference_on_scenarios.)"""
+    got = run_check(rule_check, scenario_text(scn), tmp_path)
+    hosts = next(x["hosts"] for x in qref["scenarios"] if x["name"] == scn[0])
+    left = {h: [] for h in range(len(hosts))}
+    for ln in got:
+        if ln.startswith("L "):
+            _, h, status, _, tag = ln.split()
+            assert status in ("1", "2")
+            left[int(h)].append(int(tag))
+    for h, e in enumerate(hosts):
+        assert left[h] == tags_of(e["output"]), (scn[0], h)
+
+
+class StoredKeyHeap(R.SocketHeap):
+    """Wrong model 1: the key is stored when the socket is pushed, and the smallest stored key leaves
+    (the oldest of equal ones)."""
+
+    def __init__(self):
+        super().__init__()
+        self.pushes = 0
+
+    def find(self, s):
+        return any(x[2] is s for x in self.heap)
+
+    def push(self, s):
+        self.pushes += 1
+        heapq.heappush(self.heap, (s.peek_priority(), self.pushes, s))
+
+    def pop(self):
+        return heapq.heappop(self.heap)[2]
+
+
+class TieBySlotHeap(R.SocketHeap):
+    """Wrong model 2: the reference's heap with a strict order, equal keys broken by the lower slot."""
+
+    def _smaller(self, i, j):
+        a, b = self.heap[i], self.heap[j]
+        return (a.peek_priority(), a.slot) < (b.peek_priority(), b.slot)
+
+
+def model_host(heap_cls, resift=False):
+    class ModelHost(R.Host):
+        def __init__(self, *a, **kw):
+            super().__init__(*a, **kw)
+            if self.qdisc == R.QDISC_FIFO:
+                self.q = heap_cls()
+
+        def offer(self, t, slot, pkt):
+            """Wrong model 3 (resift): a queued socket whose key changes is sifted down, then up."""
+            s = self.sockets[slot]
+            before = s.peek_priority() if resift and s.has_data() else None
+            super().offer(t, slot, pkt)
+            if before is not None and s.peek_priority() != before:
+                self.q._down(self.q.heap.index(s))
+                self.q._up(self.q.heap.index(s))
+    return ModelHost
+
+
+@pytest.mark.parametrize("model", [model_host(StoredKeyHeap), model_host(TieBySlotHeap), model_host(R.SocketHeap, resift=True)],
+                         ids=["stored_keys_global_minimum", "tie_by_lower_slot", "resift_on_key_change"])
+def test_qdisc_fixture_catches_a_wrong_heap(qref, model):
+    entries = [e for e in fixture_entries(qref) if e[1].startswith("0 ")]
+    wrong = [name for name, script, out in entries if R.replay_script(script, model) != out]
+    assert wrong, "the fixture does not tell this model from the reference"
+    # and the harness itself is sound: the plain classes through the same path agree everywhere
+    assert all(R.replay_script(script, model_host(R.SocketHeap)) == out for _, script, out in entries)

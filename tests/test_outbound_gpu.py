@@ -6,7 +6,9 @@ steps; the overload scenario as one step, as 50 ms windows and as 1 ms windows, 
 concatenated outputs; hosts 1, 3, 64, 65 with 0, 1, 63, 64, 65, 129 offers per host and step and a
 backlog across a chunk edge; 1, 2, 3, 7, 64, 65, 130 sockets per host, all queued at once; the
 hand-made boundaries (a wake exactly at `until`, a barrier offer as the first offer of the next step,
-the bootstrap boundary, local packets, an unlimited host).  Then every error with a check that nothing
+the bootstrap boundary, local packets, an unlimited host); the time-domain scenarios qdisc_*, whose
+leaving order is also compared directly with what the reference's own compiled heap and queue code
+selected (tests/golden/qdisc_reference.json).  Then every error with a check that nothing
 moved, the backlog's growth past reserve_packets, and an 8-round closed loop offers -> Outbound.step ->
 send_packets -> EventQueues.push -> pop -> Inbound.step -> next_window with both wakes folded in."""
 import heapq
@@ -85,6 +87,39 @@ def test_overload_in_one_step_and_in_windows(router, qdisc):
     outputs identical."""
     a, b, c = (S.concat_by_host(run_scenario(router, S.overload(w, qdisc)), 1) for w in (None, 50 * S.MS, 1 * S.MS))
     assert a == b == c and len(a[0]) == 600
+
+
+def tags_by_host(router, scn):
+    """The device alone: -> per host, the tags that left, concatenated over the steps."""
+    _, bw, sockets, qdisc, sim_start, boot, steps = scn
+    out = ev.Outbound(router, bw, sockets, qdisc, sim_start, boot)
+    outs = []
+    for until, per_host in steps:
+        st, tm, tg, off, res = out.step(until, *arrays(per_host))
+        outs.append((st.cpu().numpy().tolist(), u64(tm), u64(tg), u64(off), res))
+    assert out.num_queued == 0 and out.min_next_wake_ns == U64
+    out.close()
+    left = S.concat_by_host(outs, len(bw))
+    return [[g for _, _, g in left[h]] for h in range(len(bw))]
+
+
+@pytest.mark.parametrize("width", [None, 3 * S.MS], ids=["one_step", "3ms_windows"])
+@pytest.mark.parametrize("qdisc", [R.QDISC_FIFO, R.QDISC_ROUND_ROBIN], ids=["fifo", "rr"])
+def test_device_leaves_in_the_reference_programs_order(router, qdisc, width):
+    """The qdisc_* scenarios of one qdisc (two instances: their bootstrap ends differ), as one step and
+    in 3 ms windows, with no restatement in between: per host, the tags the device lets leave are the
+    tag column the reference's compiled queue code printed for that host's operations, in its order.
+    Reads tests/golden/ only."""
+    recorded = {x["name"]: x["hosts"] for x in S.load_qdisc_reference()["scenarios"]}
+    specs = S.qdisc_specs(qdisc)
+    assert len(specs) == 2 and all(spec[0] in recorded for spec in specs)
+    for spec in specs:
+        got = tags_by_host(router, S.qdisc_scenario(spec, width))
+        hosts = recorded[spec[0]]
+        assert len(got) == len(hosts)
+        for h, e in enumerate(hosts):
+            exp = [int(ln.split()[1]) for ln in e["output"].splitlines() if ln != "-"]
+            assert exp and got[h] == exp, (spec[0], h)
 
 
 def test_scenarios_reach_every_branch():
