@@ -727,6 +727,122 @@ int srg_outbound_host_state(srg_outbound* q, uint32_t host, struct srg_outbound_
  * min(*n, capacity) of them in slots[]; SRG_ERR_ARG for host >= num_hosts */
 int srg_outbound_host_order(srg_outbound* q, uint32_t host, uint32_t* slots, uint32_t capacity, uint32_t* n);
 
+/* ---- a round on the device: packet table, per-host RNG and event ids --------------------------
+ * The five calls above, joined: a round is srg_round_receive_device, the hosts run, then
+ * srg_round_send_device, and srg_next_window(result.next_start_ns, ...).  What joined them on the
+ * host before lives in HBM: each host's random generator, its event-id counter, the hosts' nodes
+ * and a packet table indexed by tag, so nothing of a round's packets crosses to the host.
+ *   Host::random          Xoshiro256PlusPlus::seed_from_u64(node_seed)     host.rs:122,233
+ *   chance                src_host.random_mut().gen::<f64>()               worker.rs:377
+ *                         = (next_u64() >> 11) * 2^-53, one generator step (rand 0.8.5)
+ *   is_completed          current_time >= sim_end_time: return, no draw    worker.rs:336-343
+ *   unknown destination   PDS_INET_DROPPED, return, no draw                worker.rs:352-368
+ *   the drop decision     after the draw; bootstrap and payload 0 draw too worker.rs:382-390
+ *   the event id          Event::new_packet inside push_packet_to_host: behind the drop return, so a
+ *                         packet dropped by loss takes none       worker.rs:422,644-654, event.rs:18-31
+ *                         the counter starts at 0 and is the host's own    host.rs:258,690-694
+ * The ids differ from the reference's by the host's local events (they share the counter); the
+ * pop order does not: ids are only compared between events of one source host, and both
+ * assignments strictly increase in that host's send order (round_rule.h derives it).
+ *   Send half: the offers are checked and completed from the packet table (total_size gathered;
+ * SRG_OFFER_LOCAL derived as dst_host == the offering host, the caller's flag byte may carry only
+ * SRG_OFFER_BARRIER), the outbound step runs, every packet that left for the router is classified
+ * and, if it draws, drawn for in its host's leaving order, the drawing packets go through the send
+ * batch (round_end_ns = until_ns) and the sent ones are pushed into the queues.
+ *   Receive half: pop(until_ns), each popped packet's total_size from the table, the inbound step.
+ *   SRG_ERR_ARG: a tag >= num_packets; a dst_host that is neither < num_hosts nor SRG_NO_HOST; a flag
+ * bit other than the barrier; a non-local packet above its DESTINATION's downstream bucket
+ * (refill + 1500; this is what makes the inbound step's size error impossible later); no packet
+ * table; whatever the composed calls refuse, with their codes (SRG_ERR_TIME_BACKWARD,
+ * SRG_ERR_EVENT_ORDER, SRG_ERR_LATENCY_RANGE).
+ *   Any call that returns an error leaves everything exactly as it was: the three parts, the
+ * generators and the counters.  packet_counts_dev is the one exception, as in
+ * srg_send_packets_device.  Both calls return after their stream work is complete.
+ *   Outputs are borrowed device pointers in the result, owned by the object: the send half's are
+ * valid until the next send, the receive half's until the next receive.  They are sized by the
+ * bounds the parts give (queued before + arrivals always suffices), so there is no capacity error.
+ *   Outside the calls: a host's other draws from the same generator (getrandom, port selection)
+ * and its local events' ids.  Between two calls the caller folds them in with srg_round_host_rng /
+ * srg_round_set_host_rng: read the state, step it, write it back.  Draws of other consumers INSIDE
+ * a step -- between two send_packet calls of one window -- are outside the call: the step draws
+ * its packets' chances back to back.                                                            */
+#define SRG_NO_HOST 0xFFFFFFFFu  /* dst_host of a packet whose destination address no host owns */
+#define SRG_ROUND_DROPPED 0      /* drew, dropped by loss */
+#define SRG_ROUND_SENT 1         /* drew, took an event id, entered its destination's queue */
+#define SRG_ROUND_LOCAL 2        /* left for the host's own address: never reaches send_packet */
+#define SRG_ROUND_AFTER_END 3    /* left at >= sim_end_ns: no draw, no id */
+#define SRG_ROUND_NO_HOST 4      /* dst_host == SRG_NO_HOST: no draw, no id */
+/* opaque; lives in the HBM of ctx's device; not thread-safe; destroy it before its ctx */
+typedef struct srg_round srg_round;
+/* host arrays [num_hosts]: host_node (the host's position in `table`, < table->n), bw_up_bits,
+ * bw_down_bits, sockets_per_host, node_seed (HostParameters::node_seed).  `table`: the struct is
+ * copied, its device arrays are borrowed for the object's life (the rules of
+ * srg_send_packets_device; packet_loss NULL: nothing is dropped, every packet still draws).
+ * reserve_packets goes to the three parts.                                                      */
+int srg_round_create(srg_ctx* ctx, uint32_t num_hosts, const uint32_t* host_node, const srg_path_table_dev* table,
+                     const uint64_t* bw_up_bits, const uint64_t* bw_down_bits, const uint32_t* sockets_per_host,
+                     int qdisc, const uint64_t* node_seed, uint64_t sim_start_ns, uint64_t bootstrap_end_ns,
+                     uint64_t sim_end_ns, uint64_t reserve_packets, srg_round** out, char* errbuf, size_t errlen);
+void srg_round_destroy(srg_round* r);
+/* The caller's packet pool, indexed by tag, borrowed (device arrays [num_packets]); may be called
+ * again when the pool grows or moves.  Entries of packets still inside the round object (in a
+ * socket, a queue or a router) must not change.                                                 */
+int srg_round_set_packets(srg_round* r, uint64_t num_packets, const uint32_t* dst_host_dev,
+                          const uint32_t* total_size_dev, const uint32_t* payload_size_dev);
+
+typedef struct srg_round_receive_result {
+    uint64_t num_popped;                     /* events popped: the inbound step's arrivals */
+    const uint64_t* popped_time_ns_dev;      /* [num_popped] grouped by host, pop order */
+    const uint64_t* popped_tag_dev;          /* [num_popped] */
+    const uint64_t* popped_host_offsets_dev; /* [num_hosts + 1] */
+    uint64_t num_leaving;                    /* = num_forwarded + num_dropped: the inbound step's outputs */
+    const uint8_t* status_dev;               /* [num_leaving] 1 forwarded, 0 dropped by CoDel */
+    const uint64_t* time_ns_dev;             /* [num_leaving] */
+    const uint64_t* tag_dev;                 /* [num_leaving] */
+    const uint64_t* host_offsets_dev;        /* [num_hosts + 1] */
+    uint64_t num_forwarded, num_dropped;
+    uint64_t num_queued_inbound, num_queued_events; /* after the call */
+    uint64_t min_next_event_ns, min_inbound_wake_ns, min_outbound_wake_ns;
+    uint64_t next_start_ns;                  /* their minimum: srg_next_window's first argument */
+    double ms_total;
+} srg_round_receive_result;
+
+int srg_round_receive_device(srg_round* r, uint64_t until_ns, void* hip_stream, srg_round_receive_result* result,
+                             char* errbuf, size_t errlen);
+
+typedef struct srg_round_send_result {
+    uint64_t num_leaving;             /* packets that left the outbound step */
+    const uint8_t* status_dev;        /* [num_leaving] SRG_ROUND_*, grouped by host, leaving order */
+    const uint64_t* time_ns_dev;      /* [num_leaving] leave time */
+    const uint64_t* tag_dev;          /* [num_leaving] */
+    const uint64_t* host_offsets_dev; /* [num_hosts + 1] */
+    uint64_t num_sent, num_dropped, num_local, num_after_end, num_no_host; /* sum = num_leaving */
+    uint64_t num_queued_outbound, num_queued_events; /* after the call */
+    uint64_t min_used_latency_ns;     /* over the sent packets, UINT64_MAX if none */
+    uint64_t min_next_event_ns, min_inbound_wake_ns, min_outbound_wake_ns;
+    uint64_t next_start_ns;           /* their minimum: srg_next_window's first argument */
+    double ms_total;
+} srg_round_send_result;
+
+/* The offers as srg_outbound_step_device takes them, without total_size (gathered by tag) and with
+ * flags_dev carrying SRG_OFFER_BARRIER only (NULL = all 0).                                      */
+int srg_round_send_device(srg_round* r, uint64_t until_ns, uint64_t num_offers, const uint64_t* time_ns_dev,
+                          const uint32_t* socket_dev, const uint64_t* priority_dev, const uint8_t* flags_dev,
+                          const uint64_t* tag_dev, const uint64_t* host_offsets_dev,
+                          uint64_t* packet_counts_dev /* may be NULL */, void* hip_stream,
+                          srg_round_send_result* result, char* errbuf, size_t errlen);
+
+/* One host's generator words and next event id: small read-back / write.  SRG_ERR_ARG for
+ * host >= num_hosts and for the all-zero state.                                                 */
+int srg_round_host_rng(srg_round* r, uint32_t host, uint64_t words[4], uint64_t* next_event_id);
+int srg_round_set_host_rng(srg_round* r, uint32_t host, const uint64_t words[4], uint64_t next_event_id);
+/* Borrowed handles of the parts, for the *_host_state / _host_order read-backs.  Stepping, pushing
+ * or popping a part through its handle, or destroying it, is a usage error: the round object owns
+ * the order of their calls.                                                                     */
+srg_event_queues* srg_round_queues(srg_round* r);
+srg_inbound* srg_round_inbound(srg_round* r);
+srg_outbound* srg_round_outbound(srg_round* r);
+
 /* ---- the routes a table's paths take; per-edge packet loads --------------------------------
  * The reference keeps no routes: petgraph's dijkstra returns scores only (mod.rs:190-208).  They
  * can be read back from a finished shortest-path table alone, because a Dijkstra label is

@@ -234,6 +234,58 @@ class OutboundHostState(ctypes.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "reserved"}
 
 
+class RoundReceiveResult(ctypes.Structure):
+    _fields_ = [
+        ("num_popped", ctypes.c_uint64),
+        ("popped_time_ns_dev", ctypes.c_void_p),
+        ("popped_tag_dev", ctypes.c_void_p),
+        ("popped_host_offsets_dev", ctypes.c_void_p),
+        ("num_leaving", ctypes.c_uint64),
+        ("status_dev", ctypes.c_void_p),
+        ("time_ns_dev", ctypes.c_void_p),
+        ("tag_dev", ctypes.c_void_p),
+        ("host_offsets_dev", ctypes.c_void_p),
+        ("num_forwarded", ctypes.c_uint64),
+        ("num_dropped", ctypes.c_uint64),
+        ("num_queued_inbound", ctypes.c_uint64),
+        ("num_queued_events", ctypes.c_uint64),
+        ("min_next_event_ns", ctypes.c_uint64),
+        ("min_inbound_wake_ns", ctypes.c_uint64),
+        ("min_outbound_wake_ns", ctypes.c_uint64),
+        ("next_start_ns", ctypes.c_uint64),
+        ("ms_total", ctypes.c_double),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if not k.endswith("_dev")}
+
+
+class RoundSendResult(ctypes.Structure):
+    _fields_ = [
+        ("num_leaving", ctypes.c_uint64),
+        ("status_dev", ctypes.c_void_p),
+        ("time_ns_dev", ctypes.c_void_p),
+        ("tag_dev", ctypes.c_void_p),
+        ("host_offsets_dev", ctypes.c_void_p),
+        ("num_sent", ctypes.c_uint64),
+        ("num_dropped", ctypes.c_uint64),
+        ("num_local", ctypes.c_uint64),
+        ("num_after_end", ctypes.c_uint64),
+        ("num_no_host", ctypes.c_uint64),
+        ("num_queued_outbound", ctypes.c_uint64),
+        ("num_queued_events", ctypes.c_uint64),
+        ("min_used_latency_ns", ctypes.c_uint64),
+        ("min_next_event_ns", ctypes.c_uint64),
+        ("min_inbound_wake_ns", ctypes.c_uint64),
+        ("min_outbound_wake_ns", ctypes.c_uint64),
+        ("next_start_ns", ctypes.c_uint64),
+        ("ms_total", ctypes.c_double),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if not k.endswith("_dev")}
+
+
 class RouteResult(ctypes.Structure):
     _fields_ = [
         ("num_pairs", ctypes.c_uint64),
@@ -307,6 +359,9 @@ EXPORTS = [
     "srg_inbound_create", "srg_inbound_destroy", "srg_inbound_step_device", "srg_inbound_host_state",
     "srg_outbound_create", "srg_outbound_destroy", "srg_outbound_step_device", "srg_outbound_host_state",
     "srg_outbound_host_order",
+    "srg_round_create", "srg_round_destroy", "srg_round_set_packets", "srg_round_receive_device",
+    "srg_round_send_device", "srg_round_host_rng", "srg_round_set_host_rng", "srg_round_queues", "srg_round_inbound",
+    "srg_round_outbound",
 ]
 
 _lib = None
@@ -435,6 +490,28 @@ def lib():
     L.srg_outbound_host_state.argtypes = [c.c_void_p, c.c_uint32, c.POINTER(OutboundHostState)]
     L.srg_outbound_host_order.restype = c.c_int
     L.srg_outbound_host_order.argtypes = [c.c_void_p, c.c_uint32, c.c_void_p, c.c_uint32, c.POINTER(c.c_uint32)]
+    L.srg_round_create.restype = c.c_int
+    L.srg_round_create.argtypes = [
+        c.c_void_p, c.c_uint32, c.c_void_p, c.POINTER(PathTableDev), c.c_void_p, c.c_void_p, c.c_void_p, c.c_int,
+        c.c_void_p, c.c_uint64, c.c_uint64, c.c_uint64, c.c_uint64, c.POINTER(c.c_void_p), c.c_char_p, c.c_size_t]
+    L.srg_round_destroy.restype = None
+    L.srg_round_destroy.argtypes = [c.c_void_p]
+    L.srg_round_set_packets.restype = c.c_int
+    L.srg_round_set_packets.argtypes = [c.c_void_p, c.c_uint64, c.c_void_p, c.c_void_p, c.c_void_p]
+    L.srg_round_receive_device.restype = c.c_int
+    L.srg_round_receive_device.argtypes = [c.c_void_p, c.c_uint64, c.c_void_p, c.POINTER(RoundReceiveResult),
+                                           c.c_char_p, c.c_size_t]
+    L.srg_round_send_device.restype = c.c_int
+    L.srg_round_send_device.argtypes = [
+        c.c_void_p, c.c_uint64, c.c_uint64, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p, c.c_void_p,
+        c.c_void_p, c.c_void_p, c.POINTER(RoundSendResult), c.c_char_p, c.c_size_t]
+    L.srg_round_host_rng.restype = c.c_int
+    L.srg_round_host_rng.argtypes = [c.c_void_p, c.c_uint32, _u64p, _u64p]
+    L.srg_round_set_host_rng.restype = c.c_int
+    L.srg_round_set_host_rng.argtypes = [c.c_void_p, c.c_uint32, _u64p, c.c_uint64]
+    for part in ("queues", "inbound", "outbound"):
+        getattr(L, "srg_round_" + part).restype = c.c_void_p
+        getattr(L, "srg_round_" + part).argtypes = [c.c_void_p]
     L.srg_next_window.restype = c.c_int
     L.srg_next_window.argtypes = [c.c_uint64, c.c_uint64, c.c_uint64, _u64p, _u64p]
     L.srg_trace_routes_device.restype = c.c_int

@@ -65,6 +65,7 @@
 #include "event_queue.hip.h"
 #include "inbound.hip.h"
 #include "outbound.hip.h"
+#include "round.hip.h"
 #include "xchg.hip.h"
 
 #include <hipcub/hipcub.hpp>
@@ -2290,6 +2291,7 @@ void direct_device(srg_ctx& c, const DevGraph& g, const uint32_t* nodes, uint32_
 #include "events_run.hip.h"
 #include "inbound_run.hip.h"
 #include "outbound_run.hip.h"
+#include "round_run.hip.h"
 #include "h2d_codec.hip.h"
 
 int guard(char* errbuf, size_t errlen, const std::function<void()>& body) {
@@ -3285,6 +3287,114 @@ int srg_outbound_host_order(srg_outbound* q, uint32_t host, uint32_t* slots, uin
     return device_call(q->ctx, nullptr, nullptr, nullptr, 0,
                        [&](hipStream_t) { out_host_order(*q, host, slots, capacity, n); });
 }
+
+int srg_round_create(srg_ctx* ctx, uint32_t num_hosts, const uint32_t* host_node, const srg_path_table_dev* table,
+                     const uint64_t* bw_up_bits, const uint64_t* bw_down_bits, const uint32_t* sockets_per_host,
+                     int qdisc, const uint64_t* node_seed, uint64_t sim_start_ns, uint64_t bootstrap_end_ns,
+                     uint64_t sim_end_ns, uint64_t reserve_packets, srg_round** out, char* errbuf, size_t errlen) {
+    if (!ctx || !out || !table ||
+        (num_hosts && (!host_node || !bw_up_bits || !bw_down_bits || !sockets_per_host || !node_seed))) {
+        set_err(errbuf, errlen, "null argument");
+        return SRG_ERR_ARG;
+    }
+    *out = nullptr;
+    if (!table->latency_ns == !table->latency_key) {
+        set_err(errbuf, errlen, "path table: exactly one of latency_ns and latency_key must be given");
+        return SRG_ERR_ARG;
+    }
+    if (table->latency_key && (!table->diag_ns || table->unit_ns < 1)) {
+        set_err(errbuf, errlen, "path table: latency_key needs diag_ns and unit_ns >= 1");
+        return SRG_ERR_ARG;
+    }
+    for (uint32_t h = 0; h < num_hosts; ++h)
+        if (host_node[h] >= table->n) {
+            set_err(errbuf, errlen, "host_node out of range (>= table->n)");
+            return SRG_ERR_ARG;
+        }
+    std::unique_ptr<srg_round> r(new (std::nothrow) srg_round);
+    if (!r) {
+        set_err(errbuf, errlen, "out of host memory");
+        return SRG_ERR_OOM;
+    }
+    r->ctx = ctx;
+    r->num_hosts = num_hosts;
+    r->bootstrap_end = bootstrap_end_ns;
+    r->sim_end = sim_end_ns;
+    r->tab = *table;
+    // the parts take ctx->mu themselves; a part that fails leaves the others to ~srg_round
+    int rc = srg_event_queues_create(ctx, num_hosts, reserve_packets, &r->q, errbuf, errlen);
+    if (rc == SRG_OK)
+        rc = srg_inbound_create(ctx, num_hosts, bw_down_bits, sim_start_ns, bootstrap_end_ns, reserve_packets, &r->inb,
+                                errbuf, errlen);
+    if (rc == SRG_OK)
+        rc = srg_outbound_create(ctx, num_hosts, bw_up_bits, sockets_per_host, qdisc, sim_start_ns, bootstrap_end_ns,
+                                 reserve_packets, &r->out, errbuf, errlen);
+    if (rc == SRG_OK) {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        rc = guard(errbuf, errlen, [&]() {
+            HIP_CHECK(hipSetDevice(ctx->device));
+            round_init(*r, host_node, node_seed);
+        });
+    }
+    if (rc == SRG_OK) *out = r.release();
+    return rc;
+}
+
+void srg_round_destroy(srg_round* r) {
+    if (!r) return;
+    {
+        std::lock_guard<std::mutex> lk(r->ctx->mu);
+        (void)hipSetDevice(r->ctx->device);
+    }
+    delete r;
+}
+
+int srg_round_set_packets(srg_round* r, uint64_t num_packets, const uint32_t* dst_host_dev,
+                          const uint32_t* total_size_dev, const uint32_t* payload_size_dev) {
+    if (!r || (num_packets && (!dst_host_dev || !total_size_dev || !payload_size_dev))) return SRG_ERR_ARG;
+    std::lock_guard<std::mutex> lk(r->ctx->mu);
+    r->pk = RoundPackets{num_packets, dst_host_dev, total_size_dev, payload_size_dev};
+    return SRG_OK;
+}
+
+int srg_round_receive_device(srg_round* r, uint64_t until_ns, void* hip_stream, srg_round_receive_result* res,
+                             char* errbuf, size_t errlen) {
+    if (!r) {
+        set_err(errbuf, errlen, "null argument");
+        return SRG_ERR_ARG;
+    }
+    return device_call(r->ctx, hip_stream, res ? &res->ms_total : nullptr, errbuf, errlen,
+                       [&](hipStream_t st) { round_receive(*r, until_ns, st, res); });
+}
+
+int srg_round_send_device(srg_round* r, uint64_t until_ns, uint64_t num_offers, const uint64_t* time_ns,
+                          const uint32_t* socket, const uint64_t* priority, const uint8_t* flags, const uint64_t* tag,
+                          const uint64_t* host_offsets, uint64_t* packet_counts, void* hip_stream,
+                          srg_round_send_result* res, char* errbuf, size_t errlen) {
+    if (!r || !host_offsets || (num_offers && (!time_ns || !socket || !priority || !tag))) {
+        set_err(errbuf, errlen, "null argument");
+        return SRG_ERR_ARG;
+    }
+    return device_call(r->ctx, hip_stream, res ? &res->ms_total : nullptr, errbuf, errlen, [&](hipStream_t st) {
+        round_send(*r, until_ns, num_offers, time_ns, socket, priority, flags, tag, host_offsets, packet_counts, st, res);
+    });
+}
+
+int srg_round_host_rng(srg_round* r, uint32_t host, uint64_t words[4], uint64_t* next_event_id) {
+    if (!r || !words || !next_event_id) return SRG_ERR_ARG;
+    return device_call(r->ctx, nullptr, nullptr, nullptr, 0,
+                       [&](hipStream_t) { round_host_rng(*r, host, words, next_event_id); });
+}
+
+int srg_round_set_host_rng(srg_round* r, uint32_t host, const uint64_t words[4], uint64_t next_event_id) {
+    if (!r || !words) return SRG_ERR_ARG;
+    return device_call(r->ctx, nullptr, nullptr, nullptr, 0,
+                       [&](hipStream_t) { round_set_host_rng(*r, host, words, next_event_id); });
+}
+
+srg_event_queues* srg_round_queues(srg_round* r) { return r ? r->q : nullptr; }
+srg_inbound* srg_round_inbound(srg_round* r) { return r ? r->inb : nullptr; }
+srg_outbound* srg_round_outbound(srg_round* r) { return r ? r->out : nullptr; }
 
 #ifdef SRG_TEST_HOOKS
 // TEST HOOK (test build only, not in the header): the device's control-law increments for counts[n]

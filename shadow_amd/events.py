@@ -20,6 +20,10 @@ EventQueues (srg_event_queues_*) keeps the per-host packet-event queues themselv
 rounds: push merges a round's ordered batch into the backlog, pop takes a window's events out in
 the reference's order (event_queue.rs:10-55, host.rs:809-818), next_window is the controller's step
 (controller.rs:88-112).
+
+Round (srg_round_*) joins the stages on the device: receive = pop -> sizes by tag -> inbound step,
+send = offers -> outbound step -> draw -> send -> push, with each host's Xoshiro256++ generator
+(host.rs:233) and event-id counter (host.rs:690) in HBM, so `chance` no longer comes from the caller.
 """
 import ctypes
 
@@ -542,3 +546,171 @@ class Outbound:
         if rc != N.SRG_OK:
             _raise(rc, "srg_outbound_host_order: host out of range")
         return [int(buf[i]) for i in range(int(n.value))]
+
+
+class _Borrowed:
+    """A device array the native library owns, seen through __cuda_array_interface__."""
+
+    def __init__(self, ptr, n, typestr):
+        self.__cuda_array_interface__ = {"shape": (int(n),), "typestr": typestr, "data": (int(ptr), False), "version": 2}
+
+
+def _borrowed(ptr, n, typestr, dtype, dev):
+    """-> an owned copy (int64 / uint8 tensor) of n elements at the borrowed device pointer."""
+    if not n or not ptr:
+        return torch.empty(0, dtype=dtype, device=dev)
+    return torch.as_tensor(_Borrowed(ptr, n, typestr), device=dev).clone()
+
+
+class _PartView:
+    """A part of a Round seen through its borrowed handle: the read-backs only."""
+
+    def __init__(self, handle, base, owner):
+        self._h, self._base, self._owner = handle, base, owner
+        self.num_hosts = owner.num_hosts
+        self.sockets_per_host = owner.sockets_per_host
+
+    def host_state(self, h):
+        return self._base.host_state(self, h)
+
+    def host_order(self, h):
+        return self._base.host_order(self, h)
+
+
+class Round:
+    """A round on the device (srg_round_*, round.hip.h): the event queues, the inbound and the outbound
+    path, each host's Xoshiro256++ generator (host.rs:233) and event-id counter (host.rs:690) and the
+    hosts' nodes in HBM, over the caller's packet table indexed by tag.  A round is
+    receive(window_end) -> the hosts run -> send(window_end, offers) -> next_window(result
+    ["next_start_ns"], ...).  An error leaves everything as it was.  The part views give host_state /
+    host_order of the round's own parts; stepping a part is not possible through them."""
+
+    def __init__(self, router, host_node, table, bw_up_bits, bw_down_bits, sockets_per_host, qdisc, node_seed,
+                 sim_start_ns, bootstrap_end_ns, sim_end_ns, reserve=0):
+        self.router = router
+        self.dev = torch.device(f"cuda:{router.device}")
+        hn = np.ascontiguousarray(host_node, dtype=np.uint32)
+        up = np.ascontiguousarray(bw_up_bits, dtype=np.uint64)
+        down = np.ascontiguousarray(bw_down_bits, dtype=np.uint64)
+        ns = np.ascontiguousarray(sockets_per_host, dtype=np.uint32)
+        seed = np.ascontiguousarray(node_seed, dtype=np.uint64)
+        if not (hn.shape == up.shape == down.shape == ns.shape == seed.shape):
+            _raise(N.SRG_ERR_ARG, "the per-host arrays differ in length")
+        self.num_hosts = int(hn.shape[0])
+        self.sockets_per_host = ns
+        self.table = table  # (keeps the borrowed device arrays alive)
+        self._packets = None
+        t = table.as_struct()
+        h = ctypes.c_void_p()
+        err = ctypes.create_string_buffer(1024)
+        rc = N.lib().srg_round_create(router._h, self.num_hosts, hn.ctypes.data, ctypes.byref(t), up.ctypes.data,
+                                      down.ctypes.data, ns.ctypes.data, int(qdisc), seed.ctypes.data, int(sim_start_ns),
+                                      int(bootstrap_end_ns), int(sim_end_ns), int(reserve), ctypes.byref(h), err, len(err))
+        if rc != N.SRG_OK:
+            _raise(rc, err.value.decode(errors="replace"))
+        self._h = h
+        L = N.lib()
+        self.queues = _PartView(ctypes.c_void_p(L.srg_round_queues(h)), EventQueues, self)
+        self.inbound = _PartView(ctypes.c_void_p(L.srg_round_inbound(h)), Inbound, self)
+        self.outbound = _PartView(ctypes.c_void_p(L.srg_round_outbound(h)), Outbound, self)
+
+    def close(self):
+        if self._h:
+            N.lib().srg_round_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_packets(self, dst_host_t, total_size_t, payload_size_t):
+        """int32 tensors [num_packets] on the device (u32 data), indexed by tag; borrowed."""
+        n = int(dst_host_t.numel())
+        assert int(total_size_t.numel()) == n and int(payload_size_t.numel()) == n
+        self._packets = (dst_host_t, total_size_t, payload_size_t)
+        rc = N.lib().srg_round_set_packets(self._h, n, dst_host_t.data_ptr() if n else None,
+                                           total_size_t.data_ptr() if n else None,
+                                           payload_size_t.data_ptr() if n else None)
+        if rc != N.SRG_OK:
+            _raise(rc, "srg_round_set_packets: null argument")
+
+    def receive_device(self, until_ns, stream=None):
+        """Raw call; returns (rc, RoundReceiveResult, message) and raises nothing."""
+        res = N.RoundReceiveResult()
+        err = ctypes.create_string_buffer(1024)
+        s = stream if stream is not None else torch.cuda.current_stream(self.dev)
+        rc = N.lib().srg_round_receive_device(self._h, int(until_ns), ctypes.c_void_p(s.cuda_stream), ctypes.byref(res),
+                                              err, len(err))
+        return rc, res, err.value.decode(errors="replace")
+
+    def receive(self, until_ns):
+        """pop(until) -> sizes -> inbound step.  Returns a dict: the result fields, the popped events
+        (popped_time, popped_tag, popped_host_offsets) and the inbound step's outputs (status uint8,
+        time, tag, host_offsets), as owned device tensors."""
+        rc, res, msg = self.receive_device(until_ns)
+        if rc != N.SRG_OK:
+            _raise_queue(rc, msg)
+        d, dev, H1 = res.as_dict(), self.dev, self.num_hosts + 1
+        d["popped_time"] = _borrowed(res.popped_time_ns_dev, res.num_popped, "<i8", torch.int64, dev)
+        d["popped_tag"] = _borrowed(res.popped_tag_dev, res.num_popped, "<i8", torch.int64, dev)
+        d["popped_host_offsets"] = _borrowed(res.popped_host_offsets_dev, H1, "<i8", torch.int64, dev)
+        d["status"] = _borrowed(res.status_dev, res.num_leaving, "|u1", torch.uint8, dev)
+        d["time"] = _borrowed(res.time_ns_dev, res.num_leaving, "<i8", torch.int64, dev)
+        d["tag"] = _borrowed(res.tag_dev, res.num_leaving, "<i8", torch.int64, dev)
+        d["host_offsets"] = _borrowed(res.host_offsets_dev, H1, "<i8", torch.int64, dev)
+        return d
+
+    def send_device(self, until_ns, num_offers, time_t, socket_t, priority_t, flags_t, tag_t, host_off_t, counts_t=None,
+                    stream=None):
+        """Raw call; returns (rc, RoundSendResult, message) and raises nothing.  time_t, priority_t,
+        tag_t, host_off_t int64, socket_t int32, flags_t uint8 (or None) tensors on the device."""
+        res = N.RoundSendResult()
+        err = ctypes.create_string_buffer(1024)
+        s = stream if stream is not None else torch.cuda.current_stream(self.dev)
+
+        def ptr(t):
+            return t.data_ptr() if t is not None else None
+        rc = N.lib().srg_round_send_device(
+            self._h, int(until_ns), int(num_offers), ptr(time_t), ptr(socket_t), ptr(priority_t), ptr(flags_t), ptr(tag_t),
+            ptr(host_off_t), ptr(counts_t), ctypes.c_void_p(s.cuda_stream), ctypes.byref(res), err, len(err))
+        return rc, res, err.value.decode(errors="replace")
+
+    def send(self, until_ns, time, socket, priority, flags, tag, host_offsets, counts=None):
+        """offers -> outbound step -> draw -> send -> push.  Device tensors (or host arrays, uploaded)
+        in.  Returns a dict: the result fields and, per leaving packet grouped by host in leaving
+        order, status (uint8, SRG_ROUND_*), time, tag and host_offsets as owned device tensors."""
+        dev = self.dev
+
+        def dev_t(a, up):
+            return a if isinstance(a, torch.Tensor) or a is None else up(np.asarray(a), dev)
+
+        def _u8(a, d):
+            return torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint8)).to(d)
+        time_t, sock_t, prio_t = dev_t(time, _i64), dev_t(socket, _i32), dev_t(priority, _i64)
+        flags_t, tag_t, off_t = dev_t(flags, _u8), dev_t(tag, _i64), dev_t(host_offsets, _i64)
+        rc, res, msg = self.send_device(until_ns, int(time_t.numel()), time_t, sock_t, prio_t, flags_t, tag_t, off_t, counts)
+        if rc != N.SRG_OK:
+            _raise_queue(rc, msg)
+        d = res.as_dict()
+        d["status"] = _borrowed(res.status_dev, res.num_leaving, "|u1", torch.uint8, dev)
+        d["time"] = _borrowed(res.time_ns_dev, res.num_leaving, "<i8", torch.int64, dev)
+        d["tag"] = _borrowed(res.tag_dev, res.num_leaving, "<i8", torch.int64, dev)
+        d["host_offsets"] = _borrowed(res.host_offsets_dev, self.num_hosts + 1, "<i8", torch.int64, dev)
+        return d
+
+    def host_rng(self, h):
+        """-> ([s0, s1, s2, s3], next_event_id) of host h."""
+        w = (ctypes.c_uint64 * 4)()
+        e = ctypes.c_uint64()
+        rc = N.lib().srg_round_host_rng(self._h, int(h), w, ctypes.byref(e))
+        if rc != N.SRG_OK:
+            _raise(rc, "srg_round_host_rng: host out of range")
+        return [int(x) for x in w], int(e.value)
+
+    def set_host_rng(self, h, words, next_event_id):
+        w = (ctypes.c_uint64 * 4)(*[int(x) for x in words])
+        rc = N.lib().srg_round_set_host_rng(self._h, int(h), w, int(next_event_id))
+        if rc != N.SRG_OK:
+            _raise(rc, "srg_round_set_host_rng: host out of range, or the all-zero state")
