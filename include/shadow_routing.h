@@ -843,6 +843,136 @@ srg_event_queues* srg_round_queues(srg_round* r);
 srg_inbound* srg_round_inbound(srg_round* r);
 srg_outbound* srg_round_outbound(srg_round* r);
 
+/* ---- interface receive: socket lookup, UDP receive buffers, tracker input counters ------------
+ * What the inbound relay does with a packet it forwards (relay/mod.rs:261-271): dst.push(packet) ->
+ *   networkinterface_push               network_interface.c:140-202: the socket associated with
+ *                                       (protocol, dst port, src ip, src port), else the one
+ *                                       associated with (protocol, dst port, 0, 0); none:
+ *                                       PDS_RCV_INTERFACE_DROPPED
+ *   inetsocket_pushInPacket             UdpSocket::push_in_packet, udp.rs:108-168: the connect() peer
+ *                                       filter on the whole SocketAddrV4 (:116-135), then the receive
+ *                                       buffer (MessageBuffer, udp.rs:1081-1157) with its soft limit
+ *   tracker_addInputBytes               if and only if a socket was found, network_interface.c:192-197,
+ *                                       tracker.c:188-252
+ * kept in HBM across steps: per socket slot (host, slot < sockets_per_host[h]) its kind, its peer,
+ * soft_limit_bytes, len_bytes and its buffered messages (tag, recv_time, payload); per host the five
+ * remote-in counters; the association table.  The interface's own address in the reference's key is
+ * constant per host: the host id stands for it.
+ *   A delivery (one packet, by tag, at time t on host h), in this order:
+ *     lookup   (h, protocol, dst_port, src_ip, src_port), else (h, protocol, dst_port, 0, 0)
+ *     none     SRG_RCV_NO_SOCKET, slot UINT32_MAX, not counted
+ *     found    counted whatever happens next: payload 0 -> packets_control += 1, bytes_control_header
+ *              += total - payload; else packets_data += 1, bytes_data_header += total - payload,
+ *              bytes_data_payload += payload (no retransmit classes, no per-socket stats; this is
+ *              the internet interface, so these are the remote-in counters)
+ *     EXTERNAL slot (the caller owns the socket's buffer, TCP for one): SRG_RCV_EXTERNAL, untouched
+ *     UDP slot has_peer and (src_ip, src_port) != peer: SRG_RCV_PEER_MISMATCH; len_bytes >=
+ *              soft_limit_bytes: SRG_RCV_FULL; else the message (tag, recv_time = t, payload) goes to
+ *              the back, len_bytes += payload: SRG_RCV_BUFFERED.  The limit is soft: one message may
+ *              carry len_bytes past it; payload 0 messages never fill a buffer; limit 0 refuses all.
+ *   A read (one recvmsg on (h, slot) at time t, udp.rs:497-546): empty -> status 0 (EWOULDBLOCK);
+ *   else status 1 and the front message's tag, recv_time and payload; it is popped (len_bytes -=
+ *   payload) unless the read carries SRG_READ_PEEK.  Truncation to the user's buffer is the caller's.
+ *   Order on a host: its deliveries in the order given, its reads in execution order, both with
+ *   non-decreasing times.  A read at t runs after every delivery with time < t, and before the
+ *   deliveries at t if and only if it carries SRG_READ_FIRST (both are local events of one
+ *   nanosecond in the reference, ordered by event id; the same one-bit answer as SRG_OFFER_BARRIER).
+ *   The buffers have no clock: nothing is checked across calls, call order is execution order.
+ *   SRG_ERR_ARG: offsets that are not monotone from 0 to the count; a tag >= num_packets; no packet
+ *        table; an unknown read flag; a read on a slot >= sockets_per_host[h] or on an EXTERNAL
+ *        slot; a read with SRG_READ_FIRST behind a read without it at the same time on one host
+ *        (the two contradict: the first ran after the deliveries at t, the second before them);
+ *        rows + reads >= 2^31
+ *   SRG_ERR_TIME_BACKWARD: a delivery (a read) earlier than its host's previous delivery (read)
+ *   Any call that returns an error leaves the state exactly as it was: buffers, counters,
+ * associations, configuration.  (The output arrays of a failed step are unspecified.)  The step
+ * returns after its stream work is complete.
+ *   Outside the calls: TCP's own receive path, the loopback interface, pcap, per-socket tracker
+ * stats, the readable / writable callbacks (derive them from the per-delivery status).          */
+#define SRG_SOCK_UDP 0
+#define SRG_SOCK_EXTERNAL 1
+#define SRG_RCV_SKIPPED 0       /* the row's status differs from deliver_status: not a delivery */
+#define SRG_RCV_NO_SOCKET 1     /* PDS_RCV_INTERFACE_DROPPED */
+#define SRG_RCV_EXTERNAL 2      /* found an EXTERNAL slot: the caller's socket takes it */
+#define SRG_RCV_PEER_MISMATCH 3 /* PDS_RCV_SOCKET_DROPPED by the peer filter */
+#define SRG_RCV_FULL 4          /* PDS_RCV_SOCKET_DROPPED by has_space */
+#define SRG_RCV_BUFFERED 5      /* PDS_RCV_SOCKET_BUFFERED */
+#define SRG_READ_PEEK 1u        /* MSG_PEEK: the message stays */
+#define SRG_READ_FIRST 2u       /* the read runs before the deliveries of its own nanosecond */
+#define SRG_SOCK_DEFAULT_RECV_BYTES 174760u /* CONFIG_RECV_BUFFER_SIZE, a new slot's soft limit */
+/* opaque; lives in the HBM of ctx's device; not thread-safe; destroy it before its ctx */
+typedef struct srg_sockets_in srg_sockets_in;
+/* sockets_per_host: host array [num_hosts], its sum below 2^31.  Every slot starts as a UDP slot
+ * without a peer, limit SRG_SOCK_DEFAULT_RECV_BYTES, empty.  reserve_messages: message storage
+ * allocated up front (growth reallocates geometrically).                                        */
+int srg_sockets_in_create(srg_ctx* ctx, uint32_t num_hosts, const uint32_t* sockets_per_host, uint64_t reserve_messages,
+                          srg_sockets_in** out, char* errbuf, size_t errlen);
+void srg_sockets_in_destroy(srg_sockets_in* q);
+/* The caller's packet pool, indexed by tag, borrowed (device arrays [num_packets]); may be called
+ * again when the pool grows or moves.  Entries of packets named by a step's rows must be valid
+ * during the step; a buffered message keeps its own tag, time and payload.                     */
+int srg_sockets_in_set_packets(srg_sockets_in* q, uint64_t num_packets, const uint8_t* protocol_dev,
+                               const uint32_t* src_ip_dev, const uint16_t* src_port_dev, const uint16_t* dst_port_dev,
+                               const uint32_t* total_size_dev, const uint32_t* payload_size_dev);
+/* Batch calls between steps, host arrays [n].  configure sets a slot's kind, peer (udp.rs:116-135)
+ * and limit; the limit of a non-empty buffer may change (set_soft_limit_bytes, udp.rs:1154); a slot
+ * named twice keeps its last entry; the buffer of a slot that becomes EXTERNAL stays as it is.
+ * associate: a key that exists already, also earlier in the same batch, is SRG_ERR_ARG
+ * (utility_debugAssert, network_interface.c:85) and nothing of the batch is added.  disassociate:
+ * a missing key is a no-op (network_interface.c:99-117).  A host >= num_hosts, a slot >=
+ * sockets_per_host[host], a kind or has_peer above 1: SRG_ERR_ARG, nothing changed.  The device
+ * table is rebuilt by the first step after a change.                                            */
+int srg_sockets_in_configure(srg_sockets_in* q, uint64_t n, const uint32_t* host, const uint32_t* slot, const uint8_t* kind,
+                             const uint8_t* has_peer, const uint32_t* peer_ip, const uint16_t* peer_port,
+                             const uint64_t* soft_limit_bytes, char* errbuf, size_t errlen);
+int srg_sockets_in_associate(srg_sockets_in* q, uint64_t n, const uint32_t* host, const uint8_t* protocol,
+                             const uint16_t* local_port, const uint32_t* peer_ip, const uint16_t* peer_port,
+                             const uint32_t* slot, char* errbuf, size_t errlen);
+int srg_sockets_in_disassociate(srg_sockets_in* q, uint64_t n, const uint32_t* host, const uint8_t* protocol,
+                                const uint16_t* local_port, const uint32_t* peer_ip, const uint16_t* peer_port,
+                                char* errbuf, size_t errlen);
+
+typedef struct srg_sockets_in_result {
+    uint64_t num_skipped, num_no_socket, num_external, num_peer_mismatch, num_full, num_buffered; /* rows per status */
+    uint64_t num_read, num_would_block; /* reads with status 1 / 0 */
+    uint64_t num_buffered_messages;     /* in all buffers, after the step */
+    double ms_total;
+} srg_sockets_in_result;
+
+/* Rows: status_dev, time_ns_dev, tag_dev, host_offsets_dev[num_hosts + 1] exactly as
+ * srg_inbound_step_device or srg_round_receive_result give them (deliver_status 1: the forwarded
+ * packets) or as srg_round_send_result gives them (deliver_status SRG_ROUND_LOCAL: the packets the
+ * relay pushes back into the interface, relay/mod.rs:263-266); a row whose status differs is
+ * skipped; status_dev NULL: every row is a delivery.  Reads: read_time_ns_dev, read_slot_dev,
+ * read_flags_dev (SRG_READ_*; NULL = all 0), read_host_offsets_dev[num_hosts + 1]; with a count of 0
+ * the arrays, offsets included, may be NULL.
+ * Outputs: out_status_dev[num_rows] SRG_RCV_*, out_slot_dev[num_rows] (UINT32_MAX: no socket or
+ * skipped); out_read_status_dev[num_reads] 1 / 0, and the message's tag, recv_time and payload
+ * (0 with status 0).                                                                            */
+int srg_sockets_in_step_device(srg_sockets_in* q, uint64_t num_rows, const uint8_t* status_dev,
+                               const uint64_t* time_ns_dev, const uint64_t* tag_dev, const uint64_t* host_offsets_dev,
+                               uint8_t deliver_status, uint64_t num_reads, const uint64_t* read_time_ns_dev,
+                               const uint32_t* read_slot_dev, const uint8_t* read_flags_dev,
+                               const uint64_t* read_host_offsets_dev, uint8_t* out_status_dev, uint32_t* out_slot_dev,
+                               uint8_t* out_read_status_dev, uint64_t* out_read_tag_dev, uint64_t* out_read_time_ns_dev,
+                               uint32_t* out_read_payload_dev, void* hip_stream, srg_sockets_in_result* result,
+                               char* errbuf, size_t errlen);
+
+/* (struct tags, not typedefs: the read-backs below have the same names) */
+struct srg_sockets_in_socket_state {
+    uint64_t len_bytes, num_messages, soft_limit_bytes;
+    uint32_t peer_ip;
+    uint16_t peer_port;
+    uint8_t kind, has_peer;
+};
+struct srg_sockets_in_host_counters {
+    uint64_t packets_control, packets_data, bytes_control_header, bytes_data_header, bytes_data_payload;
+};
+/* one small read-back each; SRG_ERR_ARG for a host or slot out of range.  reset != 0 zeroes the
+ * host's counters after reading them, as the heartbeat does (tracker.c:608).                    */
+int srg_sockets_in_socket_state(srg_sockets_in* q, uint32_t host, uint32_t slot, struct srg_sockets_in_socket_state* out);
+int srg_sockets_in_host_counters(srg_sockets_in* q, uint32_t host, struct srg_sockets_in_host_counters* out, int reset);
+
 /* ---- the routes a table's paths take; per-edge packet loads --------------------------------
  * The reference keeps no routes: petgraph's dijkstra returns scores only (mod.rs:190-208).  They
  * can be read back from a finished shortest-path table alone, because a Dijkstra label is

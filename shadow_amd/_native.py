@@ -62,6 +62,18 @@ SRG_OPT_SCAN_MIRROR_CAP = 42
 SRG_OPT_LOSS_KIND = 43
 SRG_OPT_ROUTE_TREE_ROWS = 44
 SRG_ROUTE_NONE = 0xFFFFFFFF
+SRG_SOCK_UDP = 0
+SRG_SOCK_EXTERNAL = 1
+SRG_RCV_SKIPPED = 0
+SRG_RCV_NO_SOCKET = 1
+SRG_RCV_EXTERNAL = 2
+SRG_RCV_PEER_MISMATCH = 3
+SRG_RCV_FULL = 4
+SRG_RCV_BUFFERED = 5
+SRG_READ_PEEK = 1
+SRG_READ_FIRST = 2
+SRG_SOCK_DEFAULT_RECV_BYTES = 174760
+SRG_ROUND_LOCAL = 2
 SRG_LOSS_NONE = 0
 SRG_LOSS_ROWS_LDS = 1
 SRG_LOSS_GLOBAL_ENTRIES = 2
@@ -286,6 +298,52 @@ class RoundSendResult(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if not k.endswith("_dev")}
 
 
+class SocketsInResult(ctypes.Structure):
+    _fields_ = [
+        ("num_skipped", ctypes.c_uint64),
+        ("num_no_socket", ctypes.c_uint64),
+        ("num_external", ctypes.c_uint64),
+        ("num_peer_mismatch", ctypes.c_uint64),
+        ("num_full", ctypes.c_uint64),
+        ("num_buffered", ctypes.c_uint64),
+        ("num_read", ctypes.c_uint64),
+        ("num_would_block", ctypes.c_uint64),
+        ("num_buffered_messages", ctypes.c_uint64),
+        ("ms_total", ctypes.c_double),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class SocketsInSocketState(ctypes.Structure):
+    _fields_ = [
+        ("len_bytes", ctypes.c_uint64),
+        ("num_messages", ctypes.c_uint64),
+        ("soft_limit_bytes", ctypes.c_uint64),
+        ("peer_ip", ctypes.c_uint32),
+        ("peer_port", ctypes.c_uint16),
+        ("kind", ctypes.c_uint8),
+        ("has_peer", ctypes.c_uint8),
+    ]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class SocketsInHostCounters(ctypes.Structure):
+    _fields_ = [
+        ("packets_control", ctypes.c_uint64),
+        ("packets_data", ctypes.c_uint64),
+        ("bytes_control_header", ctypes.c_uint64),
+        ("bytes_data_header", ctypes.c_uint64),
+        ("bytes_data_payload", ctypes.c_uint64),
+    ]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 class RouteResult(ctypes.Structure):
     _fields_ = [
         ("num_pairs", ctypes.c_uint64),
@@ -362,6 +420,9 @@ EXPORTS = [
     "srg_round_create", "srg_round_destroy", "srg_round_set_packets", "srg_round_receive_device",
     "srg_round_send_device", "srg_round_host_rng", "srg_round_set_host_rng", "srg_round_queues", "srg_round_inbound",
     "srg_round_outbound",
+    "srg_sockets_in_create", "srg_sockets_in_destroy", "srg_sockets_in_set_packets", "srg_sockets_in_configure",
+    "srg_sockets_in_associate", "srg_sockets_in_disassociate", "srg_sockets_in_step_device",
+    "srg_sockets_in_socket_state", "srg_sockets_in_host_counters",
 ]
 
 _lib = None
@@ -512,6 +573,27 @@ def lib():
     for part in ("queues", "inbound", "outbound"):
         getattr(L, "srg_round_" + part).restype = c.c_void_p
         getattr(L, "srg_round_" + part).argtypes = [c.c_void_p]
+    L.srg_sockets_in_create.restype = c.c_int
+    L.srg_sockets_in_create.argtypes = [c.c_void_p, c.c_uint32, c.c_void_p, c.c_uint64, c.POINTER(c.c_void_p), c.c_char_p,
+                                        c.c_size_t]
+    L.srg_sockets_in_destroy.restype = None
+    L.srg_sockets_in_destroy.argtypes = [c.c_void_p]
+    L.srg_sockets_in_set_packets.restype = c.c_int
+    L.srg_sockets_in_set_packets.argtypes = [c.c_void_p, c.c_uint64] + [c.c_void_p] * 6
+    L.srg_sockets_in_configure.restype = c.c_int
+    L.srg_sockets_in_configure.argtypes = [c.c_void_p, c.c_uint64] + [c.c_void_p] * 7 + [c.c_char_p, c.c_size_t]
+    L.srg_sockets_in_associate.restype = c.c_int
+    L.srg_sockets_in_associate.argtypes = [c.c_void_p, c.c_uint64] + [c.c_void_p] * 6 + [c.c_char_p, c.c_size_t]
+    L.srg_sockets_in_disassociate.restype = c.c_int
+    L.srg_sockets_in_disassociate.argtypes = [c.c_void_p, c.c_uint64] + [c.c_void_p] * 5 + [c.c_char_p, c.c_size_t]
+    L.srg_sockets_in_step_device.restype = c.c_int
+    L.srg_sockets_in_step_device.argtypes = (
+        [c.c_void_p, c.c_uint64] + [c.c_void_p] * 4 + [c.c_uint8, c.c_uint64] + [c.c_void_p] * 4 + [c.c_void_p] * 6 +
+        [c.c_void_p, c.POINTER(SocketsInResult), c.c_char_p, c.c_size_t])
+    L.srg_sockets_in_socket_state.restype = c.c_int
+    L.srg_sockets_in_socket_state.argtypes = [c.c_void_p, c.c_uint32, c.c_uint32, c.POINTER(SocketsInSocketState)]
+    L.srg_sockets_in_host_counters.restype = c.c_int
+    L.srg_sockets_in_host_counters.argtypes = [c.c_void_p, c.c_uint32, c.POINTER(SocketsInHostCounters), c.c_int]
     L.srg_next_window.restype = c.c_int
     L.srg_next_window.argtypes = [c.c_uint64, c.c_uint64, c.c_uint64, _u64p, _u64p]
     L.srg_trace_routes_device.restype = c.c_int

@@ -17,6 +17,7 @@
 // up them, rules in route_tree_rule.h), sections too; events_run.hip.h (the packet-event batch and
 // event-queue drivers), inbound_run.hip.h and outbound_run.hip.h (the hosts' inbound and outbound
 // paths: kernels in inbound.hip.h / outbound.hip.h, rules in inbound_rule.h / outbound_rule.h),
+// sockets_in_run.hip.h (interface receive: kernels in sockets_in.hip.h, rule in sockets_in_rule.h),
 // sections; h2d_codec.hip.h (the host entry's plain copy, H2D codec and
 // late-loss thread) and host_entry.hip.h (the host entry, stage by stage), the last two sections.
 // Still here, in order: the validation / W / certify / extract kernels, the context (srg_ctx),
@@ -66,6 +67,7 @@
 #include "inbound.hip.h"
 #include "outbound.hip.h"
 #include "round.hip.h"
+#include "sockets_in.hip.h"
 #include "xchg.hip.h"
 
 #include <hipcub/hipcub.hpp>
@@ -2292,6 +2294,7 @@ void direct_device(srg_ctx& c, const DevGraph& g, const uint32_t* nodes, uint32_
 #include "inbound_run.hip.h"
 #include "outbound_run.hip.h"
 #include "round_run.hip.h"
+#include "sockets_in_run.hip.h"
 #include "h2d_codec.hip.h"
 
 int guard(char* errbuf, size_t errlen, const std::function<void()>& body) {
@@ -3395,6 +3398,132 @@ int srg_round_set_host_rng(srg_round* r, uint32_t host, const uint64_t words[4],
 srg_event_queues* srg_round_queues(srg_round* r) { return r ? r->q : nullptr; }
 srg_inbound* srg_round_inbound(srg_round* r) { return r ? r->inb : nullptr; }
 srg_outbound* srg_round_outbound(srg_round* r) { return r ? r->out : nullptr; }
+
+int srg_sockets_in_create(srg_ctx* ctx, uint32_t num_hosts, const uint32_t* sockets_per_host, uint64_t reserve_messages,
+                          srg_sockets_in** out, char* errbuf, size_t errlen) {
+    if (!ctx || !out || (num_hosts && !sockets_per_host)) {
+        set_err(errbuf, errlen, "null argument");
+        return SRG_ERR_ARG;
+    }
+    *out = nullptr;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    return guard(errbuf, errlen, [&]() {
+        HIP_CHECK(hipSetDevice(ctx->device));
+        std::unique_ptr<srg_sockets_in> q(new srg_sockets_in);
+        q->ctx = ctx;
+        q->num_hosts = num_hosts;
+        q->sock_off_h.assign((size_t)num_hosts + 1, 0);
+        for (uint32_t h = 0; h < num_hosts; ++h) q->sock_off_h[h + 1] = q->sock_off_h[h] + sockets_per_host[h];
+        if (q->sock_off_h[num_hosts] >= (1ull << 31)) fail(SRG_ERR_ARG, "too many socket slots (>= 2^31)");
+        const uint32_t S = q->num_socks = (uint32_t)q->sock_off_h[num_hosts];
+        const size_t hb = ((size_t)num_hosts + 1) * 8, sb = ((size_t)S + 1) * 8;
+        HIP_CHECK(hipMemcpyAsync(q->sock_off.get(hb), q->sock_off_h.data(), hb, hipMemcpyHostToDevice, ctx->stream));
+        HIP_CHECK(hipMemsetAsync(q->zero_off.get(hb), 0, hb, ctx->stream));
+        for (auto& s : q->set) {
+            HIP_CHECK(hipMemsetAsync(s.off.get(sb), 0, sb, ctx->stream));
+            HIP_CHECK(hipMemsetAsync(s.counters.get((size_t)num_hosts * 40), 0, (size_t)num_hosts * 40, ctx->stream));
+            s.socks.get((size_t)S * sizeof(SinSocket));
+            s.reserve(reserve_messages);
+        }
+        if (S) {
+            k_sin_init<<<grid_for(S), kThreads, 0, ctx->stream>>>(S, (SinSocket*)q->set[0].socks.p);
+            HIP_CHECK(hipGetLastError());
+        }
+        q->coff.get(((size_t)num_hosts + 1) * 4);
+        q->ops_off.get(((size_t)S + 2) * 4);
+        q->cnt.get(sb);
+        q->sout.get((size_t)S * sizeof(SinSockOut));
+        q->red.get(sizeof(SinReduce));
+        HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        *out = q.release();
+    });
+}
+
+void srg_sockets_in_destroy(srg_sockets_in* q) {
+    if (!q) return;
+    {
+        std::lock_guard<std::mutex> lk(q->ctx->mu);
+        (void)hipSetDevice(q->ctx->device);
+    }
+    delete q;
+}
+
+int srg_sockets_in_set_packets(srg_sockets_in* q, uint64_t num_packets, const uint8_t* protocol, const uint32_t* src_ip,
+                               const uint16_t* src_port, const uint16_t* dst_port, const uint32_t* total_size,
+                               const uint32_t* payload_size) {
+    if (!q || (num_packets && (!protocol || !src_ip || !src_port || !dst_port || !total_size || !payload_size)))
+        return SRG_ERR_ARG;
+    std::lock_guard<std::mutex> lk(q->ctx->mu);
+    q->pk = SinPackets{num_packets, protocol, src_ip, src_port, dst_port, total_size, payload_size};
+    q->have_packets = true;
+    return SRG_OK;
+}
+
+int srg_sockets_in_configure(srg_sockets_in* q, uint64_t n, const uint32_t* host, const uint32_t* slot, const uint8_t* kind,
+                             const uint8_t* has_peer, const uint32_t* peer_ip, const uint16_t* peer_port,
+                             const uint64_t* soft_limit_bytes, char* errbuf, size_t errlen) {
+    if (!q || (n && (!host || !slot || !kind || !has_peer || !peer_ip || !peer_port || !soft_limit_bytes))) {
+        set_err(errbuf, errlen, "null argument");
+        return SRG_ERR_ARG;
+    }
+    return device_call(q->ctx, nullptr, nullptr, errbuf, errlen, [&](hipStream_t st) {
+        sin_configure(*q, n, host, slot, kind, has_peer, peer_ip, peer_port, soft_limit_bytes, st);
+    });
+}
+
+int srg_sockets_in_associate(srg_sockets_in* q, uint64_t n, const uint32_t* host, const uint8_t* protocol,
+                             const uint16_t* local_port, const uint32_t* peer_ip, const uint16_t* peer_port,
+                             const uint32_t* slot, char* errbuf, size_t errlen) {
+    if (!q || (n && (!host || !protocol || !local_port || !peer_ip || !peer_port || !slot))) {
+        set_err(errbuf, errlen, "null argument");
+        return SRG_ERR_ARG;
+    }
+    std::lock_guard<std::mutex> lk(q->ctx->mu);
+    return guard(errbuf, errlen, [&]() { sin_associate(*q, n, host, protocol, local_port, peer_ip, peer_port, slot); });
+}
+
+int srg_sockets_in_disassociate(srg_sockets_in* q, uint64_t n, const uint32_t* host, const uint8_t* protocol,
+                                const uint16_t* local_port, const uint32_t* peer_ip, const uint16_t* peer_port,
+                                char* errbuf, size_t errlen) {
+    if (!q || (n && (!host || !protocol || !local_port || !peer_ip || !peer_port))) {
+        set_err(errbuf, errlen, "null argument");
+        return SRG_ERR_ARG;
+    }
+    std::lock_guard<std::mutex> lk(q->ctx->mu);
+    return guard(errbuf, errlen, [&]() { sin_disassociate(*q, n, host, protocol, local_port, peer_ip, peer_port); });
+}
+
+int srg_sockets_in_step_device(srg_sockets_in* q, uint64_t num_rows, const uint8_t* status, const uint64_t* time_ns,
+                               const uint64_t* tag, const uint64_t* host_offsets, uint8_t deliver_status,
+                               uint64_t num_reads, const uint64_t* read_time_ns, const uint32_t* read_slot,
+                               const uint8_t* read_flags, const uint64_t* read_host_offsets, uint8_t* out_status,
+                               uint32_t* out_slot, uint8_t* out_read_status, uint64_t* out_read_tag,
+                               uint64_t* out_read_time_ns, uint32_t* out_read_payload, void* hip_stream,
+                               srg_sockets_in_result* res, char* errbuf, size_t errlen) {
+    if (!q || (num_rows && (!time_ns || !tag || !host_offsets || !out_status || !out_slot)) ||
+        (num_reads && (!read_time_ns || !read_slot || !read_host_offsets || !out_read_status || !out_read_tag ||
+                       !out_read_time_ns || !out_read_payload))) {
+        set_err(errbuf, errlen, "null argument");
+        return SRG_ERR_ARG;
+    }
+    return device_call(q->ctx, hip_stream, res ? &res->ms_total : nullptr, errbuf, errlen, [&](hipStream_t st) {
+        const uint64_t* zero = (const uint64_t*)q->zero_off.p;  // (no rows / no reads: the offsets may be NULL)
+        sin_step(*q, SinRows{num_rows, status, time_ns, tag, host_offsets ? host_offsets : zero, deliver_status},
+                 SinReads{num_reads, read_time_ns, read_slot, read_flags, read_host_offsets ? read_host_offsets : zero},
+                 out_status, out_slot, out_read_status, out_read_tag, out_read_time_ns, out_read_payload, st, res);
+    });
+}
+
+int srg_sockets_in_socket_state(srg_sockets_in* q, uint32_t host, uint32_t slot, struct srg_sockets_in_socket_state* out) {
+    if (!q || !out) return SRG_ERR_ARG;
+    return device_call(q->ctx, nullptr, nullptr, nullptr, 0, [&](hipStream_t) { sin_socket_state(*q, host, slot, out); });
+}
+
+int srg_sockets_in_host_counters(srg_sockets_in* q, uint32_t host, struct srg_sockets_in_host_counters* out, int reset) {
+    if (!q || !out) return SRG_ERR_ARG;
+    return device_call(q->ctx, nullptr, nullptr, nullptr, 0,
+                       [&](hipStream_t) { sin_host_counters(*q, host, out, reset); });
+}
 
 #ifdef SRG_TEST_HOOKS
 // TEST HOOK (test build only, not in the header): the device's control-law increments for counts[n]

@@ -548,6 +548,141 @@ class Outbound:
         return [int(buf[i]) for i in range(int(n.value))]
 
 
+class SocketsIn:
+    """Interface receive, resident in HBM across steps (srg_sockets_in_*, sockets_in.hip.h): what the
+    inbound relay's dst.push(packet) does (relay/mod.rs:261-271) -- the interface's socket lookup
+    (network_interface.c:140-202), the UDP sockets' receive buffers (udp.rs:108-168, 1081-1157) and the
+    tracker's remote-in counters (tracker.c:188-252) -- plus the recvmsg side of the buffers
+    (udp.rs:497-546).  step_device() takes the arrays Inbound.step_device / Round.receive_device wrote
+    (deliver_status 1) or Round.send_device wrote (deliver_status SRG_ROUND_LOCAL) untouched."""
+
+    def __init__(self, router, sockets_per_host, reserve=0):
+        self.router = router
+        self.dev = torch.device(f"cuda:{router.device}")
+        ns = np.ascontiguousarray(sockets_per_host, dtype=np.uint32)
+        self.num_hosts = int(ns.shape[0])
+        self.sockets_per_host = ns
+        self._packets = None
+        h = ctypes.c_void_p()
+        err = ctypes.create_string_buffer(1024)
+        rc = N.lib().srg_sockets_in_create(router._h, self.num_hosts, ns.ctypes.data, int(reserve), ctypes.byref(h), err,
+                                           len(err))
+        if rc != N.SRG_OK:
+            _raise(rc, err.value.decode(errors="replace"))
+        self._h = h
+        self.num_buffered_messages = 0
+
+    def close(self):
+        if self._h:
+            N.lib().srg_sockets_in_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_packets(self, protocol_t, src_ip_t, src_port_t, dst_port_t, total_size_t, payload_size_t):
+        """The packet table by tag, borrowed: uint8, int32 (u32 data), int16 (u16), int16, int32, int32
+        tensors [num_packets] on the device."""
+        ts = (protocol_t, src_ip_t, src_port_t, dst_port_t, total_size_t, payload_size_t)
+        n = int(protocol_t.numel())
+        assert all(int(t.numel()) == n for t in ts)
+        assert [t.element_size() for t in ts] == [1, 4, 2, 2, 4, 4]
+        self._packets = ts
+        rc = N.lib().srg_sockets_in_set_packets(self._h, n, *[t.data_ptr() if n else None for t in ts])
+        if rc != N.SRG_OK:
+            _raise(rc, "srg_sockets_in_set_packets: null argument")
+
+    def _batch(self, fn, cols, dtypes):
+        arrs = [np.ascontiguousarray(c, dtype=d) for c, d in zip(cols, dtypes)]
+        n = int(arrs[0].shape[0])
+        if any(int(a.shape[0]) != n for a in arrs):
+            _raise(N.SRG_ERR_ARG, "the batch's arrays differ in length")
+        err = ctypes.create_string_buffer(1024)
+        rc = fn(self._h, n, *[a.ctypes.data for a in arrs], err, len(err))
+        if rc != N.SRG_OK:
+            _raise(rc, err.value.decode(errors="replace"))
+
+    def configure(self, host, slot, kind, has_peer, peer_ip, peer_port, soft_limit_bytes):
+        """Host arrays [n]: sets each (host, slot)'s kind, peer and soft limit; all or nothing."""
+        self._batch(N.lib().srg_sockets_in_configure, (host, slot, kind, has_peer, peer_ip, peer_port, soft_limit_bytes),
+                    (np.uint32, np.uint32, np.uint8, np.uint8, np.uint32, np.uint16, np.uint64))
+
+    def associate(self, host, protocol, local_port, peer_ip, peer_port, slot):
+        """Host arrays [n]; a key that exists already raises and adds nothing."""
+        self._batch(N.lib().srg_sockets_in_associate, (host, protocol, local_port, peer_ip, peer_port, slot),
+                    (np.uint32, np.uint8, np.uint16, np.uint32, np.uint16, np.uint32))
+
+    def disassociate(self, host, protocol, local_port, peer_ip, peer_port):
+        """Host arrays [n]; a missing key is a no-op."""
+        self._batch(N.lib().srg_sockets_in_disassociate, (host, protocol, local_port, peer_ip, peer_port),
+                    (np.uint32, np.uint8, np.uint16, np.uint32, np.uint16))
+
+    def step_device(self, num_rows, status, time, tag, host_off, deliver_status, num_reads, r_time, r_slot, r_flags,
+                    r_host_off, out_status, out_slot, out_r_status, out_r_tag, out_r_time, out_r_payload, stream=None):
+        """Raw call; returns (rc, result dict, message) and raises nothing.  Every array is a device
+        tensor, a raw device pointer (int, e.g. a borrowed pointer of a Round result) or None."""
+        res = N.SocketsInResult()
+        err = ctypes.create_string_buffer(1024)
+        s = stream if stream is not None else torch.cuda.current_stream(self.dev)
+
+        def ptr(t):
+            return t.data_ptr() if isinstance(t, torch.Tensor) else (int(t) if t else None)
+        rc = N.lib().srg_sockets_in_step_device(
+            self._h, int(num_rows), ptr(status), ptr(time), ptr(tag), ptr(host_off), int(deliver_status), int(num_reads),
+            ptr(r_time), ptr(r_slot), ptr(r_flags), ptr(r_host_off), ptr(out_status), ptr(out_slot), ptr(out_r_status),
+            ptr(out_r_tag), ptr(out_r_time), ptr(out_r_payload), ctypes.c_void_p(s.cuda_stream), ctypes.byref(res), err,
+            len(err))
+        if rc == N.SRG_OK:
+            self.num_buffered_messages = int(res.num_buffered_messages)
+        return rc, res.as_dict(), err.value.decode(errors="replace")
+
+    def step(self, status, time, tag, host_offsets, deliver_status=1, r_time=None, r_slot=None, r_flags=None,
+             r_host_offsets=None):
+        """Host arrays in (status / r_flags may be None; no reads: leave r_time None), host arrays out:
+        (out_status u8, out_slot u32, read_status u8, read_tag u64, read_time u64, read_payload u32,
+        result)."""
+        dev = self.dev
+
+        def u8(a):
+            return None if a is None else torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint8)).to(dev)
+        n = int(len(time))
+        nr = 0 if r_time is None else int(len(r_time))
+        time_t, tag_t, off_t = _i64(time, dev), _i64(tag, dev), _i64(host_offsets, dev)
+        rt_t = _i64(r_time, dev) if nr else None
+        rs_t = _i32(r_slot, dev) if nr else None
+        ro_t = _i64(r_host_offsets, dev) if r_host_offsets is not None else None
+        o_st = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
+        o_sl = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+        q_st = torch.empty(max(nr, 1), dtype=torch.uint8, device=dev)
+        q_tag = torch.empty(max(nr, 1), dtype=torch.int64, device=dev)
+        q_time = torch.empty(max(nr, 1), dtype=torch.int64, device=dev)
+        q_pay = torch.empty(max(nr, 1), dtype=torch.int32, device=dev)
+        rc, res, msg = self.step_device(n, u8(status), time_t, tag_t, off_t, deliver_status, nr, rt_t, rs_t,
+                                        u8(r_flags) if nr else None, ro_t, o_st, o_sl, q_st, q_tag, q_time, q_pay)
+        if rc != N.SRG_OK:
+            _raise_queue(rc, msg)
+        return (o_st[:n].cpu().numpy(), o_sl[:n].cpu().numpy().view(np.uint32), q_st[:nr].cpu().numpy(),
+                q_tag[:nr].cpu().numpy().view(np.uint64), q_time[:nr].cpu().numpy().view(np.uint64),
+                q_pay[:nr].cpu().numpy().view(np.uint32), res)
+
+    def socket_state(self, h, slot):
+        out = N.SocketsInSocketState()
+        rc = N.lib().srg_sockets_in_socket_state(self._h, int(h), int(slot), ctypes.byref(out))
+        if rc != N.SRG_OK:
+            _raise(rc, "srg_sockets_in_socket_state: host or slot out of range")
+        return out.as_dict()
+
+    def host_counters(self, h, reset=False):
+        out = N.SocketsInHostCounters()
+        rc = N.lib().srg_sockets_in_host_counters(self._h, int(h), ctypes.byref(out), 1 if reset else 0)
+        if rc != N.SRG_OK:
+            _raise(rc, "srg_sockets_in_host_counters: host out of range")
+        return out.as_dict()
+
+
 class _Borrowed:
     """A device array the native library owns, seen through __cuda_array_interface__."""
 
