@@ -92,6 +92,16 @@ _u64p = ctypes.POINTER(ctypes.c_uint64)
 _f32p = ctypes.POINTER(ctypes.c_float)
 
 
+class _AsDict:
+    """as_dict() of the result and state structs: the fields by name, without padding (`reserved`)
+    and without borrowed device pointers (`*_dev`).  Integer fields read as int, doubles as float."""
+    _dict_keep = ()
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_
+                if k in self._dict_keep or not (k == "reserved" or k.endswith("_dev"))}
+
+
 class EdgeList(ctypes.Structure):
     _fields_ = [
         ("num_vertices", ctypes.c_uint32),
@@ -120,7 +130,7 @@ class EventBatch(ctypes.Structure):
     ]
 
 
-class EventResult(ctypes.Structure):
+class EventResult(_AsDict, ctypes.Structure):
     _fields_ = [
         ("min_next_event_ns", ctypes.c_uint64),
         ("min_used_latency_ns", ctypes.c_uint64),
@@ -128,9 +138,6 @@ class EventResult(ctypes.Structure):
         ("radix_passes", ctypes.c_uint32),
         ("ms_total", ctypes.c_double),
     ]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class PathTableDev(ctypes.Structure):
@@ -154,7 +161,7 @@ class SendBatch(ctypes.Structure):
     ]
 
 
-class SendResult(ctypes.Structure):
+class SendResult(ctypes.Structure):  # (not _AsDict: its dict is the nested ev's fields, flattened, then its own)
     _fields_ = [
         ("ev", EventResult),
         ("num_sent", ctypes.c_uint64),
@@ -167,7 +174,7 @@ class SendResult(ctypes.Structure):
         return d
 
 
-class QueueResult(ctypes.Structure):
+class QueueResult(_AsDict, ctypes.Structure):
     _fields_ = [
         ("num_moved", ctypes.c_uint64),
         ("num_queued", ctypes.c_uint64),
@@ -175,11 +182,8 @@ class QueueResult(ctypes.Structure):
         ("ms_total", ctypes.c_double),
     ]
 
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
-
-class InboundResult(ctypes.Structure):
+class InboundResult(_AsDict, ctypes.Structure):
     _fields_ = [
         ("num_forwarded", ctypes.c_uint64),
         ("num_dropped", ctypes.c_uint64),
@@ -188,11 +192,8 @@ class InboundResult(ctypes.Structure):
         ("ms_total", ctypes.c_double),
     ]
 
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
-
-class InboundHostState(ctypes.Structure):
+class InboundHostState(_AsDict, ctypes.Structure):
     _fields_ = [
         ("balance", ctypes.c_uint64),
         ("last_refill_ns", ctypes.c_uint64),
@@ -212,11 +213,8 @@ class InboundHostState(ctypes.Structure):
         ("reserved", ctypes.c_uint8 * 3),
     ]
 
-    def as_dict(self):
-        return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "reserved"}
 
-
-class OutboundResult(ctypes.Structure):
+class OutboundResult(_AsDict, ctypes.Structure):
     _fields_ = [
         ("num_sent", ctypes.c_uint64),
         ("num_local", ctypes.c_uint64),
@@ -225,11 +223,8 @@ class OutboundResult(ctypes.Structure):
         ("ms_total", ctypes.c_double),
     ]
 
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
-
-class OutboundHostState(ctypes.Structure):
+class OutboundHostState(_AsDict, ctypes.Structure):
     _fields_ = [
         ("balance", ctypes.c_uint64),
         ("last_refill_ns", ctypes.c_uint64),
@@ -242,11 +237,8 @@ class OutboundHostState(ctypes.Structure):
         ("reserved", ctypes.c_uint8 * 2),
     ]
 
-    def as_dict(self):
-        return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "reserved"}
 
-
-class RoundReceiveResult(ctypes.Structure):
+class RoundReceiveResult(_AsDict, ctypes.Structure):
     _fields_ = [
         ("num_popped", ctypes.c_uint64),
         ("popped_time_ns_dev", ctypes.c_void_p),
@@ -268,11 +260,8 @@ class RoundReceiveResult(ctypes.Structure):
         ("ms_total", ctypes.c_double),
     ]
 
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_ if not k.endswith("_dev")}
 
-
-class RoundSendResult(ctypes.Structure):
+class RoundSendResult(_AsDict, ctypes.Structure):
     _fields_ = [
         ("num_leaving", ctypes.c_uint64),
         ("status_dev", ctypes.c_void_p),
@@ -294,11 +283,8 @@ class RoundSendResult(ctypes.Structure):
         ("ms_total", ctypes.c_double),
     ]
 
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_ if not k.endswith("_dev")}
 
-
-class SocketsInResult(ctypes.Structure):
+class SocketsInResult(_AsDict, ctypes.Structure):
     _fields_ = [
         ("num_skipped", ctypes.c_uint64),
         ("num_no_socket", ctypes.c_uint64),
@@ -312,11 +298,8 @@ class SocketsInResult(ctypes.Structure):
         ("ms_total", ctypes.c_double),
     ]
 
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
-
-class SocketsInSocketState(ctypes.Structure):
+class SocketsInSocketState(_AsDict, ctypes.Structure):
     _fields_ = [
         ("len_bytes", ctypes.c_uint64),
         ("num_messages", ctypes.c_uint64),
@@ -327,11 +310,8 @@ class SocketsInSocketState(ctypes.Structure):
         ("has_peer", ctypes.c_uint8),
     ]
 
-    def as_dict(self):
-        return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
-
-class SocketsInHostCounters(ctypes.Structure):
+class SocketsInHostCounters(_AsDict, ctypes.Structure):
     _fields_ = [
         ("packets_control", ctypes.c_uint64),
         ("packets_data", ctypes.c_uint64),
@@ -340,11 +320,9 @@ class SocketsInHostCounters(ctypes.Structure):
         ("bytes_data_payload", ctypes.c_uint64),
     ]
 
-    def as_dict(self):
-        return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
-
-class RouteResult(ctypes.Structure):
+class RouteResult(_AsDict, ctypes.Structure):
+    _dict_keep = ("reserved",)  # (a scalar here, and always in the dict)
     _fields_ = [
         ("num_pairs", ctypes.c_uint64),
         ("total_hops", ctypes.c_uint64),
@@ -354,11 +332,8 @@ class RouteResult(ctypes.Structure):
         ("ms_total", ctypes.c_double),
     ]
 
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
-
-class Stats(ctypes.Structure):
+class Stats(_AsDict, ctypes.Structure):
     _fields_ = [
         ("ms_total", ctypes.c_double),
         ("ms_h2d", ctypes.c_double),
@@ -392,9 +367,6 @@ class Stats(ctypes.Structure):
         ("reserved0", ctypes.c_int32),
         ("ms_key_widen", ctypes.c_double),
     ]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 # every function declared in include/shadow_routing.h (checked by tests/test_abi.py)

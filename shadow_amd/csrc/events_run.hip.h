@@ -1,10 +1,13 @@
 // events_run.hip.h -- the host side of the packet-event batch (events.hip.h) and of the device-
 // resident per-host event queues (event_queue.hip.h): the drivers behind
-// srg_order_packet_events_device, srg_send_packets_device and srg_event_queues_*_device.  A section
+// srg_order_packet_events_device, srg_send_packets_device and srg_event_queues_*_device, and the
+// srg_event_queues_* entry points themselves (the two batch calls' stay in routing.hip).  A section
 // of routing.hip's translation unit, included there once inside its anonymous namespace (it uses
-// srg_ctx, DevBuf, fail and grid_for from the text above it); not a header to include elsewhere.
-// struct srg_event_queues is the C ABI's opaque type, so the section leaves the anonymous namespace
-// around it and enters it again.
+// srg_ctx, DevBuf, fail, grid_for, guard and device_call from the text above it and the helpers of
+// stage.hip.h); not a header to include elsewhere.  struct srg_event_queues is the C ABI's opaque
+// type and the entry points are extern "C", so the section leaves the anonymous namespace twice --
+// around the struct with create / destroy, and around push / pop behind the drivers -- and enters
+// it again.
 //
 // One batch driver serves both batch calls: event_batch_device<false> is the order call (starts at
 // the latency lookup), event_batch_device<true> the send call (the drop decision in front, the
@@ -55,10 +58,7 @@ void events_sort(srg_ctx& c, const EvIn& in, const uint64_t* deliver, const EvKe
     else
         k_ev_finish<WIDE><<<grid_for(n, 256 * 64), kThreads, 0, st>>>(k0, h0, n, f.sh_dst, in.num_hosts, host_off, flag);
     HIP_CHECK(hipMemcpyAsync(out_order, i0, n_order * 4, hipMemcpyDeviceToDevice, st));
-    uint32_t hflag = 0;
-    HIP_CHECK(hipMemcpyAsync(&hflag, flag, 4, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    if (hflag)
+    if (read_back<uint32_t>(flag, st))
         fail(SRG_ERR_EVENT_ORDER,
              "called `Option::unwrap()` on a `None` value: two packet events with equal (time, src_host_id, "
              "src_host_event_id) have no relative order");
@@ -114,9 +114,7 @@ uint64_t event_batch_device(srg_ctx& c, const EvIn& in, const EvSendIn& sx, uint
     HIP_CHECK(hipMemcpyAsync(red, &init, sizeof(EvSendReduce), hipMemcpyHostToDevice, st));
     k_ev_prep<SEND><<<grid_for(in.n, 2048), kThreads, 0, st>>>(in, sx, status, deliver, red);
     HIP_CHECK(hipGetLastError());
-    EvSendReduce sr;
-    HIP_CHECK(hipMemcpyAsync(&sr, red, sizeof(EvSendReduce), hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
+    const EvSendReduce sr = read_back<EvSendReduce>(red, st);
     const EvReduce& r = sr.r;
     ev_fail_bad(r.bad);
     const uint64_t sent = SEND ? sr.sent : in.n, drops = in.n - sent;
@@ -149,10 +147,9 @@ uint64_t event_batch_device(srg_ctx& c, const EvIn& in, const EvSendIn& sx, uint
 }  // namespace
 
 // ---- device-resident per-host event queues (event_queue.hip.h) ---------------------------
-// Two sets of resident arrays: `cur` is the queues, the other one is where a push builds the
-// merged result; it becomes `cur` only after the device flags were read (an error leaves the
-// queues as they were).  A set that is too small is simply reallocated before it is built into:
-// the contents live in the other one.
+// The stage discipline of stage.hip.h: the current set is the queues, a push builds the merged
+// result into the spare one.  A set that is too small is simply reallocated before it is built
+// into: the contents live in the other one.
 struct srg_event_queues {
     srg_ctx* ctx = nullptr;
     uint32_t num_hosts = 0;
@@ -160,20 +157,42 @@ struct srg_event_queues {
         DevBuf k0, k1, k2, tag, host_off, head;
         uint64_t cap = 0;
         EvqSet ptrs() const { return EvqSet{(uint64_t*)k0.p, (uint64_t*)k1.p, (uint64_t*)k2.p, (uint64_t*)tag.p}; }
-        void reserve(uint64_t n) {
-            if (n <= cap) return;
-            const uint64_t want = std::max(n, 2 * cap);
-            cap = 0;  // (a failed allocation leaves the set empty, not half grown)
-            for (DevBuf* b : {&k0, &k1, &k2, &tag}) b->get(want * 8);
-            cap = want;
-        }
-    } set[2];
-    int cur = 0;
+        void reserve(uint64_t n) { grow_columns(cap, n, {{&k0, 8}, {&k1, 8}, {&k2, 8}, {&tag, 8}}); }
+    };
+    TwoSets<Set> sets;
     DevBuf last_popped, bk0, bk1, bk2, btag, dead, dead_excl, part_a, part_live, new_head, cnt, offs, state, scantmp;
     uint64_t stored = 0;  // events in the current set's arrays, popped ones included
     uint64_t live = 0;
     uint64_t min_next = UINT64_MAX;
 };
+
+extern "C" {
+
+int srg_event_queues_create(srg_ctx* ctx, uint32_t num_hosts, uint64_t reserve_events, srg_event_queues** out,
+                            char* errbuf, size_t errlen) {
+    if (!ctx || !out) {
+        set_err(errbuf, errlen, "null argument");
+        return SRG_ERR_ARG;
+    }
+    *out = nullptr;
+    return stage_create(ctx, num_hosts, out, errbuf, errlen, [&](srg_event_queues& q, hipStream_t st) {
+        const size_t hb = host_row_bytes(num_hosts);
+        for (auto& s : q.sets.set) {
+            HIP_CHECK(hipMemsetAsync(s.host_off.get(hb), 0, hb, st));
+            HIP_CHECK(hipMemsetAsync(s.head.get(hb), 0, hb, st));
+            s.reserve(reserve_events);
+        }
+        HIP_CHECK(hipMemsetAsync(q.last_popped.get(hb), 0, hb, st));
+        for (DevBuf* b : {&q.dead, &q.dead_excl, &q.new_head, &q.cnt, &q.offs}) b->get(hb);
+        q.state.get(sizeof(EvqState));
+    });
+}
+
+void srg_event_queues_destroy(srg_event_queues* q) { stage_destroy(q); }
+
+uint32_t srg_event_queues_merge_tile(void) { return (uint32_t)EVQ_TILE; }
+
+}  // extern "C"
 
 namespace {
 
@@ -184,21 +203,6 @@ void evq_fill_result(const srg_event_queues& q, uint64_t moved, srg_queue_result
     res->min_next_event_ns = q.min_next;
 }
 
-void evq_scan(srg_event_queues& q, const uint64_t* in, uint64_t* out, hipStream_t st) {
-    const int n = (int)q.num_hosts + 1;
-    size_t tb = 0;
-    HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, in, out, n, st));
-    void* tmp = q.scantmp.get(tb);
-    HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(tmp, tb, in, out, n, st));
-}
-
-EvqState evq_read_state(EvqState* dev, hipStream_t st) {
-    EvqState s;
-    HIP_CHECK(hipMemcpyAsync(&s, dev, sizeof(EvqState), hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    return s;
-}
-
 void evq_push(srg_event_queues& q, const srg_event_batch* b, const uint64_t* deliver, const uint32_t* order,
               uint64_t nb, const uint64_t* tag, hipStream_t st, srg_queue_result* res) {
     evq_fill_result(q, 0, res);
@@ -206,8 +210,8 @@ void evq_push(srg_event_queues& q, const srg_event_batch* b, const uint64_t* del
     if (nb > b->num_events) fail(SRG_ERR_ARG, "num_order exceeds the batch's num_events");
     if (b->num_events >= 0xFFFFFFFFull) fail(SRG_ERR_ARG, "event batch too large (>= 2^32 events)");
     const uint32_t H = q.num_hosts;
-    srg_event_queues::Set& A = q.set[q.cur];
-    srg_event_queues::Set& O = q.set[q.cur ^ 1];
+    srg_event_queues::Set& A = q.sets.current();
+    srg_event_queues::Set& O = q.sets.spare();
     const EvqSet B{(uint64_t*)q.bk0.get(nb * 8), (uint64_t*)q.bk1.get(nb * 8), (uint64_t*)q.bk2.get(nb * 8),
                    (uint64_t*)q.btag.get(nb * 8)};
     EvqState* ds = (EvqState*)q.state.get(sizeof(EvqState));
@@ -216,7 +220,7 @@ void evq_push(srg_event_queues& q, const srg_event_batch* b, const uint64_t* del
     const EvqGatherIn gi{b->num_events, nb, order, b->dst_host, b->src_host, b->src_event_id, deliver, tag, H};
     k_evq_gather<<<grid_for(nb, 2048), kThreads, 0, st>>>(gi, B, (const uint64_t*)q.last_popped.p, ds);
     HIP_CHECK(hipGetLastError());
-    EvqState s = evq_read_state(ds, st);
+    EvqState s = read_back<EvqState>(ds, st);
     if (s.flags & EVQ_BAD_ORDER)
         fail(SRG_ERR_ARG,
              "order is not the batch's queue order (an entry >= num_events, a dst_host >= num_hosts, or keys "
@@ -232,7 +236,8 @@ void evq_push(srg_event_queues& q, const srg_event_batch* b, const uint64_t* del
     uint64_t* dead = (uint64_t*)q.dead.p;
     uint64_t* dead_excl = (uint64_t*)q.dead_excl.p;
     k_evq_dead<<<grid_for((size_t)H + 1), kThreads, 0, st>>>(a_off, a_head, H, dead);
-    evq_scan(q, dead, dead_excl, st);
+    // (const input: the iterator type this scan has always been instantiated with, see exclusive_sum)
+    exclusive_sum(q.scantmp, (const uint64_t*)dead, dead_excl, (int)H + 1, st);
     const uint64_t ntiles = (n + EVQ_TILE - 1) / EVQ_TILE;
     if (ntiles >= 0x7FFFFFFFull) fail(SRG_ERR_ARG, "event queues too large for one merge launch");
     uint64_t* part_a = (uint64_t*)q.part_a.get((ntiles + 1) * 8);
@@ -245,12 +250,12 @@ void evq_push(srg_event_queues& q, const srg_event_batch* b, const uint64_t* del
     k_evq_min<<<grid_for(H, 2048), kThreads, 0, st>>>(O.ptrs(), (const uint64_t*)O.host_off.p,
                                                       (const uint64_t*)O.head.p, H, ds);
     HIP_CHECK(hipGetLastError());
-    s = evq_read_state(ds, st);
+    s = read_back<EvqState>(ds, st);
     if (s.flags & EVQ_EQUAL_KEYS)
         fail(SRG_ERR_EVENT_ORDER,
              "called `Option::unwrap()` on a `None` value: two packet events with equal (time, src_host_id, "
              "src_host_event_id) have no relative order");
-    q.cur ^= 1;
+    q.sets.flip();
     q.stored = q.live = n_out;
     q.min_next = s.min_head;
     evq_fill_result(q, nb, res);
@@ -260,7 +265,7 @@ void evq_pop(srg_event_queues& q, uint64_t until, uint64_t capacity, uint64_t* o
              uint64_t* out_id, uint64_t* out_tag, uint64_t* out_off, hipStream_t st, srg_queue_result* res) {
     evq_fill_result(q, 0, res);
     const uint32_t H = q.num_hosts;
-    srg_event_queues::Set& A = q.set[q.cur];
+    srg_event_queues::Set& A = q.sets.current();
     uint64_t* host_off = (uint64_t*)A.host_off.p;
     uint64_t* head = (uint64_t*)A.head.p;
     uint64_t* new_head = (uint64_t*)q.new_head.p;
@@ -268,10 +273,8 @@ void evq_pop(srg_event_queues& q, uint64_t until, uint64_t capacity, uint64_t* o
     uint64_t* offs = (uint64_t*)q.offs.p;
     k_evq_pop_find<<<grid_for((size_t)H + 1, 2048), kThreads, 0, st>>>(A.ptrs(), host_off, head, H, until, new_head, cnt);
     HIP_CHECK(hipGetLastError());
-    evq_scan(q, cnt, offs, st);
-    uint64_t total = 0;
-    HIP_CHECK(hipMemcpyAsync(&total, offs + H, 8, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
+    exclusive_sum(q.scantmp, (const uint64_t*)cnt, offs, (int)H + 1, st);  // (const: as above)
+    const uint64_t total = read_back<uint64_t>(offs + H, st);
     if (total > capacity) {
         if (res) res->num_moved = total;
         fail(SRG_ERR_ARG, "out_capacity too small: " + std::to_string(total) + " events are due (nothing popped)");
@@ -289,8 +292,40 @@ void evq_pop(srg_event_queues& q, uint64_t until, uint64_t capacity, uint64_t* o
     k_evq_pop_commit<<<grid_for(H, 2048), kThreads, 0, st>>>(A.ptrs(), host_off, head, (uint64_t*)q.last_popped.p,
                                                              new_head, H, ds);
     HIP_CHECK(hipGetLastError());
-    const EvqState s = evq_read_state(ds, st);
+    const EvqState s = read_back<EvqState>(ds, st);
     q.live -= total;
     q.min_next = s.min_head;
     evq_fill_result(q, total, res);
 }
+
+}  // namespace
+
+extern "C" {
+
+int srg_event_queues_push_device(srg_event_queues* q, const srg_event_batch* b, const uint64_t* deliver,
+                                 const uint32_t* order, uint64_t num_order, const uint64_t* tag, void* hip_stream,
+                                 srg_queue_result* res, char* errbuf, size_t errlen) {
+    if (!q || !b ||
+        (num_order && (!deliver || !order || !b->src_host || !b->dst_host || !b->src_event_id))) {
+        set_err(errbuf, errlen, "null argument");
+        return SRG_ERR_ARG;
+    }
+    return device_call(q->ctx, hip_stream, res ? &res->ms_total : nullptr, errbuf, errlen,
+                       [&](hipStream_t st) { evq_push(*q, b, deliver, order, num_order, tag, st, res); });
+}
+
+int srg_event_queues_pop_device(srg_event_queues* q, uint64_t until_ns, uint64_t out_capacity, uint64_t* out_time,
+                                uint32_t* out_src, uint64_t* out_id, uint64_t* out_tag, uint64_t* out_off,
+                                void* hip_stream, srg_queue_result* res, char* errbuf, size_t errlen) {
+    if (!q || (out_capacity && (!out_time || !out_tag || !out_off))) {
+        set_err(errbuf, errlen, "null argument");
+        return SRG_ERR_ARG;
+    }
+    return device_call(q->ctx, hip_stream, res ? &res->ms_total : nullptr, errbuf, errlen, [&](hipStream_t st) {
+        evq_pop(*q, until_ns, out_capacity, out_time, out_src, out_id, out_tag, out_off, st, res);
+    });
+}
+
+}  // extern "C"
+
+namespace {

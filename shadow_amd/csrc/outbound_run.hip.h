@@ -1,14 +1,15 @@
 // outbound_run.hip.h -- the host side of the hosts' outbound path (outbound.hip.h): the driver behind
-// srg_outbound_step_device and the small read-backs of srg_outbound_host_state / _host_order.  A
-// section of routing.hip's translation unit, included there once inside its anonymous namespace (it
-// uses srg_ctx, DevBuf, fail and grid_for from the text above it); not a header to include elsewhere.
-// struct srg_outbound is the C ABI's opaque type, so the section leaves the anonymous namespace
-// around it and enters it again.
+// srg_outbound_step_device and the small read-backs of srg_outbound_host_state / _host_order, and the
+// srg_outbound_* entry points themselves.  A section of routing.hip's translation unit, included
+// there once inside its anonymous namespace (it uses srg_ctx, DevBuf, fail, grid_for and device_call
+// from the text above it and the helpers of stage.hip.h); not a header to include elsewhere.  struct
+// srg_outbound is the C ABI's opaque type and the entry points are extern "C", so the section leaves
+// the anonymous namespace around them and enters it again.
 //
-// Two sets of resident arrays, as in the inbound path: `cur` is the state, the other one is where a
-// step builds its result; it becomes `cur` only after the device flags and totals were read (an
-// error leaves the state as it was).  Every path that queued work synchronises `st` before it
-// returns.
+// The stage discipline of stage.hip.h: the current set is the state, a step builds its result into
+// the spare one and flips after the device flags and totals were read.  The round's send undoes a
+// step that succeeded: snapshot() / restore().  Every path that queued work synchronises `st` before
+// it returns.
 
 }  // namespace
 
@@ -31,41 +32,91 @@ struct srg_outbound {
                               (uint64_t*)tag.p,  (uint32_t*)next.p, (uint64_t*)host_off.p};
         }
         void reserve(uint64_t n) {
-            if (n <= cap) return;
-            const uint64_t want = std::max(n, 2 * cap);
-            cap = 0;  // (a failed allocation leaves the set empty, not half grown)
-            slot.get(want * 4);
-            prio.get(want * 8);
-            size.get(want * 4);
-            flags.get(want);
-            tag.get(want * 8);
-            next.get(want * 4);
-            cap = want;
+            grow_columns(cap, n, {{&slot, 4}, {&prio, 8}, {&size, 4}, {&flags, 1}, {&tag, 8}, {&next, 4}});
         }
-    } set[2];
-    int cur = 0;
+    };
+    TwoSets<Set> sets;
     DevBuf inc, seg_off, lnk, gone, newidx, o_idx, o_time, o_status, cnt, rem, offs, red, scantmp;
-    uint64_t backlog = 0;  // packets in the current set's backlog arrays
-    uint64_t cached = 0;   // hosts whose relay holds a cached packet
-    uint64_t min_wake = UINT64_MAX;
+    // What a step changes on the host side.  A snapshot is all of it and which set is current: the
+    // spare set still holds the previous state until the next step builds into it.
+    struct Counters {
+        uint64_t backlog = 0;  // packets in the current set's backlog arrays
+        uint64_t cached = 0;   // hosts whose relay holds a cached packet
+        uint64_t min_wake = UINT64_MAX;
+    } ctr;
+    struct Snapshot {
+        int cur;
+        Counters ctr;
+    };
+    Snapshot snapshot() const { return Snapshot{sets.cur, ctr}; }
+    void restore(const Snapshot& s) {
+        sets.cur = s.cur;
+        ctr = s.ctr;
+    }
 };
 
-namespace {
+extern "C" {
 
-void out_scan(srg_outbound& q, const uint64_t* in, uint64_t* out, hipStream_t st) {
-    const int n = (int)q.num_hosts + 1;
-    size_t tb = 0;
-    HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, in, out, n, st));
-    void* tmp = q.scantmp.get(tb);
-    HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(tmp, tb, in, out, n, st));
+int srg_outbound_create(srg_ctx* ctx, uint32_t num_hosts, const uint64_t* bw_up_bits, const uint32_t* sockets_per_host,
+                        int qdisc, uint64_t sim_start_ns, uint64_t bootstrap_end_ns, uint64_t reserve_packets,
+                        srg_outbound** out, char* errbuf, size_t errlen) {
+    if (!ctx || !out || (num_hosts && (!bw_up_bits || !sockets_per_host))) {
+        set_err(errbuf, errlen, "null argument");
+        return SRG_ERR_ARG;
+    }
+    *out = nullptr;
+    if (!sim_start_ok(sim_start_ns, errbuf, errlen)) return SRG_ERR_ARG;
+    if (qdisc != SRG_QDISC_FIFO && qdisc != SRG_QDISC_ROUND_ROBIN) {
+        set_err(errbuf, errlen, "qdisc is neither SRG_QDISC_FIFO nor SRG_QDISC_ROUND_ROBIN");
+        return SRG_ERR_ARG;
+    }
+    for (uint32_t h = 0; h < num_hosts; ++h)
+        if (sockets_per_host[h] >= (1u << 31)) {
+            set_err(errbuf, errlen, "sockets_per_host outside the domain (>= 2^31)");
+            return SRG_ERR_ARG;
+        }
+    return stage_create(ctx, num_hosts, out, errbuf, errlen, [&](srg_outbound& q, hipStream_t st) {
+        q.qdisc = qdisc;
+        q.sim_start = sim_start_ns;
+        q.bootstrap_end = bootstrap_end_ns;
+        q.seg_off_host.assign((size_t)num_hosts + 1, 0);
+        for (uint32_t h = 0; h < num_hosts; ++h) q.seg_off_host[h + 1] = q.seg_off_host[h] + sockets_per_host[h];
+        const uint64_t slots = q.seg_off_host[num_hosts];
+        const size_t hb = host_row_bytes(num_hosts);
+        for (auto& s : q.sets.set) {
+            HIP_CHECK(hipMemsetAsync(s.host_off.get(hb), 0, hb, st));
+            s.hosts.get((size_t)num_hosts * sizeof(OutHost));
+            for (DevBuf* b : {&s.ord, &s.ch, &s.ct, &s.dh, &s.dt}) b->get(slots * 4);
+            s.nprio.get(slots * 8);
+            s.reserve(reserve_packets);
+        }
+        for (DevBuf* b : {&q.cnt, &q.rem, &q.offs}) b->get(hb);
+        q.red.get(sizeof(OutReduce));
+        HIP_CHECK(hipMemcpyAsync(q.seg_off.get(hb), q.seg_off_host.data(), hb, hipMemcpyHostToDevice, st));
+        uint64_t* inc = (uint64_t*)q.inc.get((size_t)num_hosts * 8);
+        if (num_hosts) {
+            uint64_t* bw = (uint64_t*)q.o_time.get((size_t)num_hosts * 8);
+            HIP_CHECK(hipMemcpyAsync(bw, bw_up_bits, (size_t)num_hosts * 8, hipMemcpyHostToDevice, st));
+            k_out_init<<<grid_for(std::max<uint64_t>(num_hosts, slots)), kThreads, 0, st>>>(
+                bw, num_hosts, slots, sim_start_ns, inc, (OutHost*)q.sets.set[0].hosts.p, (OutHost*)q.sets.set[1].hosts.p,
+                q.sets.set[0].seg(), q.sets.set[1].seg());
+            HIP_CHECK(hipGetLastError());
+        }
+    });
 }
+
+void srg_outbound_destroy(srg_outbound* q) { stage_destroy(q); }
+
+}  // extern "C"
+
+namespace {
 
 void out_fill_result(const srg_outbound& q, uint64_t sent, uint64_t local, srg_outbound_result* res) {
     if (!res) return;
     res->num_sent = sent;
     res->num_local = local;
-    res->num_queued = q.backlog + q.cached;
-    res->min_next_wake_ns = q.min_wake;
+    res->num_queued = q.ctr.backlog + q.ctr.cached;
+    res->min_next_wake_ns = q.ctr.min_wake;
 }
 
 void out_step(srg_outbound& q, uint64_t until, const OutOffers& A, uint64_t capacity, uint8_t* out_status,
@@ -74,10 +125,10 @@ void out_step(srg_outbound& q, uint64_t until, const OutOffers& A, uint64_t capa
     if (until > INB_TIME_END) fail(SRG_ERR_ARG, "until_ns outside the time domain (> 2^62)");
     const uint32_t H = q.num_hosts;
     // a host's packets are indexed in 32 bits (OUT_NIL is the end of a FIFO)
-    if (A.n >= (1ull << 32) || q.backlog + A.n + H >= 0xffffffffull)
+    if (A.n >= (1ull << 32) || q.ctr.backlog + A.n + H >= 0xffffffffull)
         fail(SRG_ERR_ARG, "too many packets in one step (queued + offers must stay below 2^32)");
-    srg_outbound::Set& C = q.set[q.cur];
-    srg_outbound::Set& O = q.set[q.cur ^ 1];
+    srg_outbound::Set& C = q.sets.current();
+    srg_outbound::Set& O = q.sets.spare();
     OutReduce* dred = (OutReduce*)q.red.p;
     const OutReduce init{~0ull, 0ull, 0ull, 0ull, 0u, 0u};
     HIP_CHECK(hipMemcpyAsync(dred, &init, sizeof(OutReduce), hipMemcpyHostToDevice, st));
@@ -87,9 +138,7 @@ void out_step(srg_outbound& q, uint64_t until, const OutOffers& A, uint64_t capa
     k_out_validate<<<grid_for(std::max<uint64_t>(A.n, (uint64_t)H + 1), 2048), kThreads, 0, st>>>(
         A, (const OutHost*)C.hosts.p, (const uint64_t*)q.inc.p, seg_off, H, q.sim_start, until, dred);
     HIP_CHECK(hipGetLastError());
-    OutReduce r;
-    HIP_CHECK(hipMemcpyAsync(&r, dred, sizeof(OutReduce), hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
+    OutReduce r = read_back<OutReduce>(dred, st);
     if (r.flags & OUT_BAD_OFFSETS) fail(SRG_ERR_ARG, "host_offsets are not monotone from 0 to num_offers");
     if (r.flags & OUT_BAD_TIME)
         fail(SRG_ERR_ARG, "an offer's time is outside [sim_start_ns, 2^62) or not below until_ns");
@@ -101,7 +150,7 @@ void out_step(srg_outbound& q, uint64_t until, const OutOffers& A, uint64_t capa
              "a non-local packet is larger than its host's token bucket (refill + 1500): it would never conform");
     if (r.flags & OUT_TIME_BACKWARD)
         fail(SRG_ERR_TIME_BACKWARD, "an offer is earlier than its host's previous offer or its last executed forward task");
-    const uint64_t nseq = q.backlog + A.n;
+    const uint64_t nseq = q.ctr.backlog + A.n;
     OutScratch X;
     X.lnk = (uint32_t*)q.lnk.get(nseq * 4);
     X.gone = (uint8_t*)q.gone.get(nseq);
@@ -119,13 +168,13 @@ void out_step(srg_outbound& q, uint64_t until, const OutOffers& A, uint64_t capa
                                                       (const uint64_t*)q.inc.p, seg_off, C.seg(), O.seg(), C.ptrs(), A, X, H,
                                                       q.qdisc, until, q.bootstrap_end, cnt, rem, dred);
     HIP_CHECK(hipGetLastError());
-    out_scan(q, cnt, offs, st);
-    out_scan(q, rem, new_off, st);
-    uint64_t total = 0, kept = 0;
+    // (const inputs: the iterator type these scans have always been instantiated with, see exclusive_sum)
+    exclusive_sum(q.scantmp, (const uint64_t*)cnt, offs, (int)H + 1, st);
+    exclusive_sum(q.scantmp, (const uint64_t*)rem, new_off, (int)H + 1, st);
+    uint64_t total = 0, kept = 0;  // (the two totals ride in the record's synchronise)
     HIP_CHECK(hipMemcpyAsync(&total, offs + H, 8, hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipMemcpyAsync(&kept, new_off + H, 8, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipMemcpyAsync(&r, dred, sizeof(OutReduce), hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
+    r = read_back<OutReduce>(dred, st);
     if (total > capacity) {
         if (res) {
             res->num_sent = r.sent;
@@ -142,17 +191,15 @@ void out_step(srg_outbound& q, uint64_t until, const OutOffers& A, uint64_t capa
         HIP_CHECK(hipGetLastError());
     }
     HIP_CHECK(hipStreamSynchronize(st));
-    q.cur ^= 1;
-    q.backlog = kept;
-    q.cached = r.cached;
-    q.min_wake = r.min_wake;
+    q.sets.flip();
+    q.ctr = srg_outbound::Counters{kept, r.cached, r.min_wake};
     out_fill_result(q, r.sent, r.local, res);
 }
 
 OutHost out_read_host(srg_outbound& q, uint32_t host) {
     if (host >= q.num_hosts) fail(SRG_ERR_ARG, "host out of range (>= num_hosts)");
     OutHost s;
-    HIP_CHECK(hipMemcpy(&s, (const OutHost*)q.set[q.cur].hosts.p + host, sizeof(OutHost), hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(&s, (const OutHost*)q.sets.current().hosts.p + host, sizeof(OutHost), hipMemcpyDeviceToHost));
     return s;
 }
 
@@ -176,7 +223,42 @@ void out_host_order(srg_outbound& q, uint32_t host, uint32_t* slots, uint32_t ca
     const uint32_t cap = (uint32_t)(q.seg_off_host[host + 1] - s0);
     if (!s.qlen || !capacity) return;
     std::vector<uint32_t> ord(cap);
-    HIP_CHECK(hipMemcpy(ord.data(), (const uint32_t*)q.set[q.cur].ord.p + s0, (size_t)cap * 4, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(ord.data(), (const uint32_t*)q.sets.current().ord.p + s0, (size_t)cap * 4, hipMemcpyDeviceToHost));
     for (uint32_t i = 0; i < s.qlen && i < capacity; ++i)
         slots[i] = ord[q.qdisc == OUT_QDISC_ROUND_ROBIN ? (s.rr_head + i) % cap : i];
 }
+
+}  // namespace
+
+extern "C" {
+
+int srg_outbound_step_device(srg_outbound* q, uint64_t until_ns, uint64_t num_offers, const uint64_t* time_ns,
+                             const uint32_t* socket, const uint64_t* priority, const uint32_t* total_size,
+                             const uint8_t* flags, const uint64_t* tag, const uint64_t* host_offsets, uint64_t out_capacity,
+                             uint8_t* out_status, uint64_t* out_time, uint64_t* out_tag, uint64_t* out_off, void* hip_stream,
+                             srg_outbound_result* res, char* errbuf, size_t errlen) {
+    if (!q || !host_offsets || (num_offers && (!time_ns || !socket || !priority || !total_size || !tag)) ||
+        (out_capacity && (!out_status || !out_time || !out_tag || !out_off))) {
+        set_err(errbuf, errlen, "null argument");
+        return SRG_ERR_ARG;
+    }
+    return device_call(q->ctx, hip_stream, res ? &res->ms_total : nullptr, errbuf, errlen, [&](hipStream_t st) {
+        out_step(*q, until_ns, OutOffers{num_offers, time_ns, socket, priority, total_size, flags, tag, host_offsets},
+                 out_capacity, out_status, out_time, out_tag, out_off, st, res);
+    });
+}
+
+int srg_outbound_host_state(srg_outbound* q, uint32_t host, struct srg_outbound_host_state* out) {
+    if (!q || !out) return SRG_ERR_ARG;
+    return device_call(q->ctx, nullptr, nullptr, nullptr, 0, [&](hipStream_t) { out_host_state(*q, host, out); });
+}
+
+int srg_outbound_host_order(srg_outbound* q, uint32_t host, uint32_t* slots, uint32_t capacity, uint32_t* n) {
+    if (!q || !n || (capacity && !slots)) return SRG_ERR_ARG;
+    return device_call(q->ctx, nullptr, nullptr, nullptr, 0,
+                       [&](hipStream_t) { out_host_order(*q, host, slots, capacity, n); });
+}
+
+}  // extern "C"
+
+namespace {

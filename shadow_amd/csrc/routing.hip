@@ -14,15 +14,18 @@
 // choose_sparse), sections of this translation unit; the device headers (kernels, tight_sparse,
 // sparse, sparse_ds, events, event_queue, xchg); routes.hip.h (route tracing and link loads over a
 // finished table, rule in route_rule.h) and route_trees.hip.h (whole route trees and loads pushed
-// up them, rules in route_tree_rule.h), sections too; events_run.hip.h (the packet-event batch and
-// event-queue drivers), inbound_run.hip.h and outbound_run.hip.h (the hosts' inbound and outbound
-// paths: kernels in inbound.hip.h / outbound.hip.h, rules in inbound_rule.h / outbound_rule.h),
-// sockets_in_run.hip.h (interface receive: kernels in sockets_in.hip.h, rule in sockets_in_rule.h),
-// sections; h2d_codec.hip.h (the host entry's plain copy, H2D codec and
-// late-loss thread) and host_entry.hip.h (the host entry, stage by stage), the last two sections.
+// up them, rules in route_tree_rule.h), sections too; stage.hip.h (what the resident stages share:
+// scan, grow, read-back, the two sets, create / destroy) and the stages, each with its srg_*
+// entry points beside its struct and drivers: events_run.hip.h (the packet-event batch and the
+// event queues), inbound_run.hip.h and outbound_run.hip.h (the hosts' inbound and outbound paths:
+// kernels in inbound.hip.h / outbound.hip.h, rules in inbound_rule.h / outbound_rule.h),
+// round_run.hip.h (a round over the three), sockets_in_run.hip.h (interface receive: kernels in
+// sockets_in.hip.h, rule in sockets_in_rule.h); h2d_codec.hip.h (the host entry's plain copy, H2D
+// codec and late-loss thread) and host_entry.hip.h (the host entry, stage by stage), the last two
+// sections.
 // Still here, in order: the validation / W / certify / extract kernels, the context (srg_ctx),
 // prelude(), HostSink, the FW schedules (stream_hop, fw_blocked, SymFw, FwOverlap),
-// compute_device, direct paths, guard(), device_call(), extern "C".
+// compute_device, direct paths, guard(), device_call(), the rest of extern "C".
 // No CPU fallback: every entry point fails loudly (status code) when HIP is unavailable.
 #include <hip/hip_runtime.h>
 #include <hsa/hsa.h>
@@ -2290,13 +2293,6 @@ void direct_device(srg_ctx& c, const DevGraph& g, const uint32_t* nodes, uint32_
     }
 }
 
-#include "events_run.hip.h"
-#include "inbound_run.hip.h"
-#include "outbound_run.hip.h"
-#include "round_run.hip.h"
-#include "sockets_in_run.hip.h"
-#include "h2d_codec.hip.h"
-
 int guard(char* errbuf, size_t errlen, const std::function<void()>& body) {
     try {
         body();
@@ -2335,6 +2331,14 @@ int device_call(srg_ctx* ctx, void* hip_stream, double* ms_total, char* errbuf, 
     if (ms_total) *ms_total = ms_since(t0);
     return rc;
 }
+
+#include "stage.hip.h"
+#include "events_run.hip.h"
+#include "inbound_run.hip.h"
+#include "outbound_run.hip.h"
+#include "round_run.hip.h"
+#include "sockets_in_run.hip.h"
+#include "h2d_codec.hip.h"
 
 #include "host_entry.hip.h"
 }  // namespace
@@ -3062,485 +3066,6 @@ int srg_send_packets_device(srg_ctx* ctx, const srg_send_batch* sb, const srg_pa
         }
     });
 }
-
-int srg_event_queues_create(srg_ctx* ctx, uint32_t num_hosts, uint64_t reserve_events, srg_event_queues** out,
-                            char* errbuf, size_t errlen) {
-    if (!ctx || !out) {
-        set_err(errbuf, errlen, "null argument");
-        return SRG_ERR_ARG;
-    }
-    *out = nullptr;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    return guard(errbuf, errlen, [&]() {
-        HIP_CHECK(hipSetDevice(ctx->device));
-        std::unique_ptr<srg_event_queues> q(new srg_event_queues);
-        q->ctx = ctx;
-        q->num_hosts = num_hosts;
-        const size_t hb = ((size_t)num_hosts + 1) * 8;
-        for (auto& s : q->set) {
-            HIP_CHECK(hipMemsetAsync(s.host_off.get(hb), 0, hb, ctx->stream));
-            HIP_CHECK(hipMemsetAsync(s.head.get(hb), 0, hb, ctx->stream));
-            s.reserve(reserve_events);
-        }
-        HIP_CHECK(hipMemsetAsync(q->last_popped.get(hb), 0, hb, ctx->stream));
-        for (DevBuf* b : {&q->dead, &q->dead_excl, &q->new_head, &q->cnt, &q->offs}) b->get(hb);
-        q->state.get(sizeof(EvqState));
-        HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        *out = q.release();
-    });
-}
-
-void srg_event_queues_destroy(srg_event_queues* q) {
-    if (!q) return;
-    {
-        std::lock_guard<std::mutex> lk(q->ctx->mu);
-        (void)hipSetDevice(q->ctx->device);
-    }
-    delete q;
-}
-
-uint32_t srg_event_queues_merge_tile(void) { return (uint32_t)EVQ_TILE; }
-
-int srg_event_queues_push_device(srg_event_queues* q, const srg_event_batch* b, const uint64_t* deliver,
-                                 const uint32_t* order, uint64_t num_order, const uint64_t* tag, void* hip_stream,
-                                 srg_queue_result* res, char* errbuf, size_t errlen) {
-    if (!q || !b ||
-        (num_order && (!deliver || !order || !b->src_host || !b->dst_host || !b->src_event_id))) {
-        set_err(errbuf, errlen, "null argument");
-        return SRG_ERR_ARG;
-    }
-    return device_call(q->ctx, hip_stream, res ? &res->ms_total : nullptr, errbuf, errlen,
-                       [&](hipStream_t st) { evq_push(*q, b, deliver, order, num_order, tag, st, res); });
-}
-
-int srg_event_queues_pop_device(srg_event_queues* q, uint64_t until_ns, uint64_t out_capacity, uint64_t* out_time,
-                                uint32_t* out_src, uint64_t* out_id, uint64_t* out_tag, uint64_t* out_off,
-                                void* hip_stream, srg_queue_result* res, char* errbuf, size_t errlen) {
-    if (!q || (out_capacity && (!out_time || !out_tag || !out_off))) {
-        set_err(errbuf, errlen, "null argument");
-        return SRG_ERR_ARG;
-    }
-    return device_call(q->ctx, hip_stream, res ? &res->ms_total : nullptr, errbuf, errlen, [&](hipStream_t st) {
-        evq_pop(*q, until_ns, out_capacity, out_time, out_src, out_id, out_tag, out_off, st, res);
-    });
-}
-
-int srg_inbound_create(srg_ctx* ctx, uint32_t num_hosts, const uint64_t* bw_down_bits, uint64_t sim_start_ns,
-                       uint64_t bootstrap_end_ns, uint64_t reserve_packets, srg_inbound** out, char* errbuf,
-                       size_t errlen) {
-    if (!ctx || !out || (num_hosts && !bw_down_bits)) {
-        set_err(errbuf, errlen, "null argument");
-        return SRG_ERR_ARG;
-    }
-    *out = nullptr;
-    if (sim_start_ns >= INB_TIME_END) {
-        set_err(errbuf, errlen, "sim_start_ns outside the time domain (>= 2^62)");
-        return SRG_ERR_ARG;
-    }
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    return guard(errbuf, errlen, [&]() {
-        HIP_CHECK(hipSetDevice(ctx->device));
-        std::unique_ptr<srg_inbound> q(new srg_inbound);
-        q->ctx = ctx;
-        q->num_hosts = num_hosts;
-        q->sim_start = sim_start_ns;
-        q->bootstrap_end = bootstrap_end_ns;
-        const size_t hb = ((size_t)num_hosts + 1) * 8;
-        for (auto& s : q->set) {
-            HIP_CHECK(hipMemsetAsync(s.host_off.get(hb), 0, hb, ctx->stream));
-            s.hosts.get((size_t)num_hosts * sizeof(InbHost));
-            s.reserve(reserve_packets);
-        }
-        for (DevBuf* b : {&q->cnt, &q->rem, &q->offs}) b->get(hb);
-        q->hout.get((size_t)num_hosts * sizeof(InbHostOut));
-        q->red.get(sizeof(InbReduce));
-        uint64_t* inc = (uint64_t*)q->inc.get((size_t)num_hosts * 8);
-        if (num_hosts) {
-            uint64_t* bw = (uint64_t*)q->scr_time.get((size_t)num_hosts * 8);
-            HIP_CHECK(hipMemcpyAsync(bw, bw_down_bits, (size_t)num_hosts * 8, hipMemcpyHostToDevice, ctx->stream));
-            k_inb_init<<<grid_for(num_hosts), kThreads, 0, ctx->stream>>>(bw, num_hosts, sim_start_ns, inc,
-                                                                          (InbHost*)q->set[0].hosts.p,
-                                                                          (InbHost*)q->set[1].hosts.p);
-            HIP_CHECK(hipGetLastError());
-        }
-        HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        *out = q.release();
-    });
-}
-
-void srg_inbound_destroy(srg_inbound* q) {
-    if (!q) return;
-    {
-        std::lock_guard<std::mutex> lk(q->ctx->mu);
-        (void)hipSetDevice(q->ctx->device);
-    }
-    delete q;
-}
-
-int srg_inbound_step_device(srg_inbound* q, uint64_t until_ns, uint64_t num_arrivals, const uint64_t* time_ns,
-                            const uint32_t* total_size, const uint64_t* tag, const uint64_t* host_offsets,
-                            uint64_t out_capacity, uint8_t* out_status, uint64_t* out_time, uint64_t* out_tag,
-                            uint64_t* out_off, void* hip_stream, srg_inbound_result* res, char* errbuf, size_t errlen) {
-    if (!q || !host_offsets || (num_arrivals && (!time_ns || !total_size || !tag)) ||
-        (out_capacity && (!out_status || !out_time || !out_tag || !out_off))) {
-        set_err(errbuf, errlen, "null argument");
-        return SRG_ERR_ARG;
-    }
-    return device_call(q->ctx, hip_stream, res ? &res->ms_total : nullptr, errbuf, errlen, [&](hipStream_t st) {
-        inb_step(*q, until_ns, InbArrivals{num_arrivals, time_ns, total_size, tag, host_offsets}, out_capacity,
-                 out_status, out_time, out_tag, out_off, st, res);
-    });
-}
-
-int srg_inbound_host_state(srg_inbound* q, uint32_t host, struct srg_inbound_host_state* out) {
-    if (!q || !out) return SRG_ERR_ARG;
-    return device_call(q->ctx, nullptr, nullptr, nullptr, 0, [&](hipStream_t) { inb_host_state(*q, host, out); });
-}
-
-int srg_outbound_create(srg_ctx* ctx, uint32_t num_hosts, const uint64_t* bw_up_bits, const uint32_t* sockets_per_host,
-                        int qdisc, uint64_t sim_start_ns, uint64_t bootstrap_end_ns, uint64_t reserve_packets,
-                        srg_outbound** out, char* errbuf, size_t errlen) {
-    if (!ctx || !out || (num_hosts && (!bw_up_bits || !sockets_per_host))) {
-        set_err(errbuf, errlen, "null argument");
-        return SRG_ERR_ARG;
-    }
-    *out = nullptr;
-    if (sim_start_ns >= INB_TIME_END) {
-        set_err(errbuf, errlen, "sim_start_ns outside the time domain (>= 2^62)");
-        return SRG_ERR_ARG;
-    }
-    if (qdisc != SRG_QDISC_FIFO && qdisc != SRG_QDISC_ROUND_ROBIN) {
-        set_err(errbuf, errlen, "qdisc is neither SRG_QDISC_FIFO nor SRG_QDISC_ROUND_ROBIN");
-        return SRG_ERR_ARG;
-    }
-    for (uint32_t h = 0; h < num_hosts; ++h)
-        if (sockets_per_host[h] >= (1u << 31)) {
-            set_err(errbuf, errlen, "sockets_per_host outside the domain (>= 2^31)");
-            return SRG_ERR_ARG;
-        }
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    return guard(errbuf, errlen, [&]() {
-        HIP_CHECK(hipSetDevice(ctx->device));
-        std::unique_ptr<srg_outbound> q(new srg_outbound);
-        q->ctx = ctx;
-        q->num_hosts = num_hosts;
-        q->qdisc = qdisc;
-        q->sim_start = sim_start_ns;
-        q->bootstrap_end = bootstrap_end_ns;
-        q->seg_off_host.assign((size_t)num_hosts + 1, 0);
-        for (uint32_t h = 0; h < num_hosts; ++h) q->seg_off_host[h + 1] = q->seg_off_host[h] + sockets_per_host[h];
-        const uint64_t slots = q->seg_off_host[num_hosts];
-        const size_t hb = ((size_t)num_hosts + 1) * 8;
-        for (auto& s : q->set) {
-            HIP_CHECK(hipMemsetAsync(s.host_off.get(hb), 0, hb, ctx->stream));
-            s.hosts.get((size_t)num_hosts * sizeof(OutHost));
-            for (DevBuf* b : {&s.ord, &s.ch, &s.ct, &s.dh, &s.dt}) b->get(slots * 4);
-            s.nprio.get(slots * 8);
-            s.reserve(reserve_packets);
-        }
-        for (DevBuf* b : {&q->cnt, &q->rem, &q->offs}) b->get(hb);
-        q->red.get(sizeof(OutReduce));
-        HIP_CHECK(hipMemcpyAsync(q->seg_off.get(hb), q->seg_off_host.data(), hb, hipMemcpyHostToDevice, ctx->stream));
-        uint64_t* inc = (uint64_t*)q->inc.get((size_t)num_hosts * 8);
-        if (num_hosts) {
-            uint64_t* bw = (uint64_t*)q->o_time.get((size_t)num_hosts * 8);
-            HIP_CHECK(hipMemcpyAsync(bw, bw_up_bits, (size_t)num_hosts * 8, hipMemcpyHostToDevice, ctx->stream));
-            k_out_init<<<grid_for(std::max<uint64_t>(num_hosts, slots)), kThreads, 0, ctx->stream>>>(
-                bw, num_hosts, slots, sim_start_ns, inc, (OutHost*)q->set[0].hosts.p, (OutHost*)q->set[1].hosts.p,
-                q->set[0].seg(), q->set[1].seg());
-            HIP_CHECK(hipGetLastError());
-        }
-        HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        *out = q.release();
-    });
-}
-
-void srg_outbound_destroy(srg_outbound* q) {
-    if (!q) return;
-    {
-        std::lock_guard<std::mutex> lk(q->ctx->mu);
-        (void)hipSetDevice(q->ctx->device);
-    }
-    delete q;
-}
-
-int srg_outbound_step_device(srg_outbound* q, uint64_t until_ns, uint64_t num_offers, const uint64_t* time_ns,
-                             const uint32_t* socket, const uint64_t* priority, const uint32_t* total_size,
-                             const uint8_t* flags, const uint64_t* tag, const uint64_t* host_offsets, uint64_t out_capacity,
-                             uint8_t* out_status, uint64_t* out_time, uint64_t* out_tag, uint64_t* out_off, void* hip_stream,
-                             srg_outbound_result* res, char* errbuf, size_t errlen) {
-    if (!q || !host_offsets || (num_offers && (!time_ns || !socket || !priority || !total_size || !tag)) ||
-        (out_capacity && (!out_status || !out_time || !out_tag || !out_off))) {
-        set_err(errbuf, errlen, "null argument");
-        return SRG_ERR_ARG;
-    }
-    return device_call(q->ctx, hip_stream, res ? &res->ms_total : nullptr, errbuf, errlen, [&](hipStream_t st) {
-        out_step(*q, until_ns, OutOffers{num_offers, time_ns, socket, priority, total_size, flags, tag, host_offsets},
-                 out_capacity, out_status, out_time, out_tag, out_off, st, res);
-    });
-}
-
-int srg_outbound_host_state(srg_outbound* q, uint32_t host, struct srg_outbound_host_state* out) {
-    if (!q || !out) return SRG_ERR_ARG;
-    return device_call(q->ctx, nullptr, nullptr, nullptr, 0, [&](hipStream_t) { out_host_state(*q, host, out); });
-}
-
-int srg_outbound_host_order(srg_outbound* q, uint32_t host, uint32_t* slots, uint32_t capacity, uint32_t* n) {
-    if (!q || !n || (capacity && !slots)) return SRG_ERR_ARG;
-    return device_call(q->ctx, nullptr, nullptr, nullptr, 0,
-                       [&](hipStream_t) { out_host_order(*q, host, slots, capacity, n); });
-}
-
-int srg_round_create(srg_ctx* ctx, uint32_t num_hosts, const uint32_t* host_node, const srg_path_table_dev* table,
-                     const uint64_t* bw_up_bits, const uint64_t* bw_down_bits, const uint32_t* sockets_per_host,
-                     int qdisc, const uint64_t* node_seed, uint64_t sim_start_ns, uint64_t bootstrap_end_ns,
-                     uint64_t sim_end_ns, uint64_t reserve_packets, srg_round** out, char* errbuf, size_t errlen) {
-    if (!ctx || !out || !table ||
-        (num_hosts && (!host_node || !bw_up_bits || !bw_down_bits || !sockets_per_host || !node_seed))) {
-        set_err(errbuf, errlen, "null argument");
-        return SRG_ERR_ARG;
-    }
-    *out = nullptr;
-    if (!table->latency_ns == !table->latency_key) {
-        set_err(errbuf, errlen, "path table: exactly one of latency_ns and latency_key must be given");
-        return SRG_ERR_ARG;
-    }
-    if (table->latency_key && (!table->diag_ns || table->unit_ns < 1)) {
-        set_err(errbuf, errlen, "path table: latency_key needs diag_ns and unit_ns >= 1");
-        return SRG_ERR_ARG;
-    }
-    for (uint32_t h = 0; h < num_hosts; ++h)
-        if (host_node[h] >= table->n) {
-            set_err(errbuf, errlen, "host_node out of range (>= table->n)");
-            return SRG_ERR_ARG;
-        }
-    std::unique_ptr<srg_round> r(new (std::nothrow) srg_round);
-    if (!r) {
-        set_err(errbuf, errlen, "out of host memory");
-        return SRG_ERR_OOM;
-    }
-    r->ctx = ctx;
-    r->num_hosts = num_hosts;
-    r->bootstrap_end = bootstrap_end_ns;
-    r->sim_end = sim_end_ns;
-    r->tab = *table;
-    // the parts take ctx->mu themselves; a part that fails leaves the others to ~srg_round
-    int rc = srg_event_queues_create(ctx, num_hosts, reserve_packets, &r->q, errbuf, errlen);
-    if (rc == SRG_OK)
-        rc = srg_inbound_create(ctx, num_hosts, bw_down_bits, sim_start_ns, bootstrap_end_ns, reserve_packets, &r->inb,
-                                errbuf, errlen);
-    if (rc == SRG_OK)
-        rc = srg_outbound_create(ctx, num_hosts, bw_up_bits, sockets_per_host, qdisc, sim_start_ns, bootstrap_end_ns,
-                                 reserve_packets, &r->out, errbuf, errlen);
-    if (rc == SRG_OK) {
-        std::lock_guard<std::mutex> lk(ctx->mu);
-        rc = guard(errbuf, errlen, [&]() {
-            HIP_CHECK(hipSetDevice(ctx->device));
-            round_init(*r, host_node, node_seed);
-        });
-    }
-    if (rc == SRG_OK) *out = r.release();
-    return rc;
-}
-
-void srg_round_destroy(srg_round* r) {
-    if (!r) return;
-    {
-        std::lock_guard<std::mutex> lk(r->ctx->mu);
-        (void)hipSetDevice(r->ctx->device);
-    }
-    delete r;
-}
-
-int srg_round_set_packets(srg_round* r, uint64_t num_packets, const uint32_t* dst_host_dev,
-                          const uint32_t* total_size_dev, const uint32_t* payload_size_dev) {
-    if (!r || (num_packets && (!dst_host_dev || !total_size_dev || !payload_size_dev))) return SRG_ERR_ARG;
-    std::lock_guard<std::mutex> lk(r->ctx->mu);
-    r->pk = RoundPackets{num_packets, dst_host_dev, total_size_dev, payload_size_dev};
-    return SRG_OK;
-}
-
-int srg_round_receive_device(srg_round* r, uint64_t until_ns, void* hip_stream, srg_round_receive_result* res,
-                             char* errbuf, size_t errlen) {
-    if (!r) {
-        set_err(errbuf, errlen, "null argument");
-        return SRG_ERR_ARG;
-    }
-    return device_call(r->ctx, hip_stream, res ? &res->ms_total : nullptr, errbuf, errlen,
-                       [&](hipStream_t st) { round_receive(*r, until_ns, st, res); });
-}
-
-int srg_round_send_device(srg_round* r, uint64_t until_ns, uint64_t num_offers, const uint64_t* time_ns,
-                          const uint32_t* socket, const uint64_t* priority, const uint8_t* flags, const uint64_t* tag,
-                          const uint64_t* host_offsets, uint64_t* packet_counts, void* hip_stream,
-                          srg_round_send_result* res, char* errbuf, size_t errlen) {
-    if (!r || !host_offsets || (num_offers && (!time_ns || !socket || !priority || !tag))) {
-        set_err(errbuf, errlen, "null argument");
-        return SRG_ERR_ARG;
-    }
-    return device_call(r->ctx, hip_stream, res ? &res->ms_total : nullptr, errbuf, errlen, [&](hipStream_t st) {
-        round_send(*r, until_ns, num_offers, time_ns, socket, priority, flags, tag, host_offsets, packet_counts, st, res);
-    });
-}
-
-int srg_round_host_rng(srg_round* r, uint32_t host, uint64_t words[4], uint64_t* next_event_id) {
-    if (!r || !words || !next_event_id) return SRG_ERR_ARG;
-    return device_call(r->ctx, nullptr, nullptr, nullptr, 0,
-                       [&](hipStream_t) { round_host_rng(*r, host, words, next_event_id); });
-}
-
-int srg_round_set_host_rng(srg_round* r, uint32_t host, const uint64_t words[4], uint64_t next_event_id) {
-    if (!r || !words) return SRG_ERR_ARG;
-    return device_call(r->ctx, nullptr, nullptr, nullptr, 0,
-                       [&](hipStream_t) { round_set_host_rng(*r, host, words, next_event_id); });
-}
-
-srg_event_queues* srg_round_queues(srg_round* r) { return r ? r->q : nullptr; }
-srg_inbound* srg_round_inbound(srg_round* r) { return r ? r->inb : nullptr; }
-srg_outbound* srg_round_outbound(srg_round* r) { return r ? r->out : nullptr; }
-
-int srg_sockets_in_create(srg_ctx* ctx, uint32_t num_hosts, const uint32_t* sockets_per_host, uint64_t reserve_messages,
-                          srg_sockets_in** out, char* errbuf, size_t errlen) {
-    if (!ctx || !out || (num_hosts && !sockets_per_host)) {
-        set_err(errbuf, errlen, "null argument");
-        return SRG_ERR_ARG;
-    }
-    *out = nullptr;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    return guard(errbuf, errlen, [&]() {
-        HIP_CHECK(hipSetDevice(ctx->device));
-        std::unique_ptr<srg_sockets_in> q(new srg_sockets_in);
-        q->ctx = ctx;
-        q->num_hosts = num_hosts;
-        q->sock_off_h.assign((size_t)num_hosts + 1, 0);
-        for (uint32_t h = 0; h < num_hosts; ++h) q->sock_off_h[h + 1] = q->sock_off_h[h] + sockets_per_host[h];
-        if (q->sock_off_h[num_hosts] >= (1ull << 31)) fail(SRG_ERR_ARG, "too many socket slots (>= 2^31)");
-        const uint32_t S = q->num_socks = (uint32_t)q->sock_off_h[num_hosts];
-        const size_t hb = ((size_t)num_hosts + 1) * 8, sb = ((size_t)S + 1) * 8;
-        HIP_CHECK(hipMemcpyAsync(q->sock_off.get(hb), q->sock_off_h.data(), hb, hipMemcpyHostToDevice, ctx->stream));
-        HIP_CHECK(hipMemsetAsync(q->zero_off.get(hb), 0, hb, ctx->stream));
-        for (auto& s : q->set) {
-            HIP_CHECK(hipMemsetAsync(s.off.get(sb), 0, sb, ctx->stream));
-            HIP_CHECK(hipMemsetAsync(s.counters.get((size_t)num_hosts * 40), 0, (size_t)num_hosts * 40, ctx->stream));
-            s.socks.get((size_t)S * sizeof(SinSocket));
-            s.reserve(reserve_messages);
-        }
-        if (S) {
-            k_sin_init<<<grid_for(S), kThreads, 0, ctx->stream>>>(S, (SinSocket*)q->set[0].socks.p);
-            HIP_CHECK(hipGetLastError());
-        }
-        q->coff.get(((size_t)num_hosts + 1) * 4);
-        q->ops_off.get(((size_t)S + 2) * 4);
-        q->cnt.get(sb);
-        q->sout.get((size_t)S * sizeof(SinSockOut));
-        q->red.get(sizeof(SinReduce));
-        HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        *out = q.release();
-    });
-}
-
-void srg_sockets_in_destroy(srg_sockets_in* q) {
-    if (!q) return;
-    {
-        std::lock_guard<std::mutex> lk(q->ctx->mu);
-        (void)hipSetDevice(q->ctx->device);
-    }
-    delete q;
-}
-
-int srg_sockets_in_set_packets(srg_sockets_in* q, uint64_t num_packets, const uint8_t* protocol, const uint32_t* src_ip,
-                               const uint16_t* src_port, const uint16_t* dst_port, const uint32_t* total_size,
-                               const uint32_t* payload_size) {
-    if (!q || (num_packets && (!protocol || !src_ip || !src_port || !dst_port || !total_size || !payload_size)))
-        return SRG_ERR_ARG;
-    std::lock_guard<std::mutex> lk(q->ctx->mu);
-    q->pk = SinPackets{num_packets, protocol, src_ip, src_port, dst_port, total_size, payload_size};
-    q->have_packets = true;
-    return SRG_OK;
-}
-
-int srg_sockets_in_configure(srg_sockets_in* q, uint64_t n, const uint32_t* host, const uint32_t* slot, const uint8_t* kind,
-                             const uint8_t* has_peer, const uint32_t* peer_ip, const uint16_t* peer_port,
-                             const uint64_t* soft_limit_bytes, char* errbuf, size_t errlen) {
-    if (!q || (n && (!host || !slot || !kind || !has_peer || !peer_ip || !peer_port || !soft_limit_bytes))) {
-        set_err(errbuf, errlen, "null argument");
-        return SRG_ERR_ARG;
-    }
-    return device_call(q->ctx, nullptr, nullptr, errbuf, errlen, [&](hipStream_t st) {
-        sin_configure(*q, n, host, slot, kind, has_peer, peer_ip, peer_port, soft_limit_bytes, st);
-    });
-}
-
-int srg_sockets_in_associate(srg_sockets_in* q, uint64_t n, const uint32_t* host, const uint8_t* protocol,
-                             const uint16_t* local_port, const uint32_t* peer_ip, const uint16_t* peer_port,
-                             const uint32_t* slot, char* errbuf, size_t errlen) {
-    if (!q || (n && (!host || !protocol || !local_port || !peer_ip || !peer_port || !slot))) {
-        set_err(errbuf, errlen, "null argument");
-        return SRG_ERR_ARG;
-    }
-    std::lock_guard<std::mutex> lk(q->ctx->mu);
-    return guard(errbuf, errlen, [&]() { sin_associate(*q, n, host, protocol, local_port, peer_ip, peer_port, slot); });
-}
-
-int srg_sockets_in_disassociate(srg_sockets_in* q, uint64_t n, const uint32_t* host, const uint8_t* protocol,
-                                const uint16_t* local_port, const uint32_t* peer_ip, const uint16_t* peer_port,
-                                char* errbuf, size_t errlen) {
-    if (!q || (n && (!host || !protocol || !local_port || !peer_ip || !peer_port))) {
-        set_err(errbuf, errlen, "null argument");
-        return SRG_ERR_ARG;
-    }
-    std::lock_guard<std::mutex> lk(q->ctx->mu);
-    return guard(errbuf, errlen, [&]() { sin_disassociate(*q, n, host, protocol, local_port, peer_ip, peer_port); });
-}
-
-int srg_sockets_in_step_device(srg_sockets_in* q, uint64_t num_rows, const uint8_t* status, const uint64_t* time_ns,
-                               const uint64_t* tag, const uint64_t* host_offsets, uint8_t deliver_status,
-                               uint64_t num_reads, const uint64_t* read_time_ns, const uint32_t* read_slot,
-                               const uint8_t* read_flags, const uint64_t* read_host_offsets, uint8_t* out_status,
-                               uint32_t* out_slot, uint8_t* out_read_status, uint64_t* out_read_tag,
-                               uint64_t* out_read_time_ns, uint32_t* out_read_payload, void* hip_stream,
-                               srg_sockets_in_result* res, char* errbuf, size_t errlen) {
-    if (!q || (num_rows && (!time_ns || !tag || !host_offsets || !out_status || !out_slot)) ||
-        (num_reads && (!read_time_ns || !read_slot || !read_host_offsets || !out_read_status || !out_read_tag ||
-                       !out_read_time_ns || !out_read_payload))) {
-        set_err(errbuf, errlen, "null argument");
-        return SRG_ERR_ARG;
-    }
-    return device_call(q->ctx, hip_stream, res ? &res->ms_total : nullptr, errbuf, errlen, [&](hipStream_t st) {
-        const uint64_t* zero = (const uint64_t*)q->zero_off.p;  // (no rows / no reads: the offsets may be NULL)
-        sin_step(*q, SinRows{num_rows, status, time_ns, tag, host_offsets ? host_offsets : zero, deliver_status},
-                 SinReads{num_reads, read_time_ns, read_slot, read_flags, read_host_offsets ? read_host_offsets : zero},
-                 out_status, out_slot, out_read_status, out_read_tag, out_read_time_ns, out_read_payload, st, res);
-    });
-}
-
-int srg_sockets_in_socket_state(srg_sockets_in* q, uint32_t host, uint32_t slot, struct srg_sockets_in_socket_state* out) {
-    if (!q || !out) return SRG_ERR_ARG;
-    return device_call(q->ctx, nullptr, nullptr, nullptr, 0, [&](hipStream_t) { sin_socket_state(*q, host, slot, out); });
-}
-
-int srg_sockets_in_host_counters(srg_sockets_in* q, uint32_t host, struct srg_sockets_in_host_counters* out, int reset) {
-    if (!q || !out) return SRG_ERR_ARG;
-    return device_call(q->ctx, nullptr, nullptr, nullptr, 0,
-                       [&](hipStream_t) { sin_host_counters(*q, host, out, reset); });
-}
-
-#ifdef SRG_TEST_HOOKS
-// TEST HOOK (test build only, not in the header): the device's control-law increments for counts[n]
-int srg_test_inbound_control_law(srg_ctx* ctx, const uint64_t* counts, uint32_t n, uint64_t* out) {
-    if (!ctx || !counts || !out || !n) return SRG_ERR_ARG;
-    return device_call(ctx, nullptr, nullptr, nullptr, 0, [&](hipStream_t st) {
-        DevBuf in, res;
-        in.get((size_t)n * 8);
-        res.get((size_t)n * 8);
-        HIP_CHECK(hipMemcpyAsync(in.p, counts, (size_t)n * 8, hipMemcpyHostToDevice, st));
-        k_inb_test_law<<<grid_for(n), kThreads, 0, st>>>((const uint64_t*)in.p, n, (uint64_t*)res.p);
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpyAsync(out, res.p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipStreamSynchronize(st));
-    });
-}
-#endif
 
 int srg_trace_routes_device(srg_ctx* ctx, const srg_edge_list* g, const srg_path_table_dev* t, const uint32_t* src,
                             const uint32_t* dst, uint64_t num_pairs, uint64_t hop_capacity, uint64_t* out_off,

@@ -49,6 +49,22 @@ def _i64(a, dev):
     return torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint64).view(np.int64)).to(dev)
 
 
+def _u8(a, dev):
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint8)).to(dev)
+
+
+def _ptr(t):
+    """A device tensor, a raw device pointer (int, e.g. a borrowed pointer of a Round result) or None."""
+    return t.data_ptr() if isinstance(t, torch.Tensor) else (int(t) if t else None)
+
+
+def _dev_t(a, up, dev):
+    """a as it is when it is a device tensor or None; a host array or host tensor is uploaded by up (_i32, _i64, _u8)."""
+    if a is None or (isinstance(a, torch.Tensor) and a.is_cuda):
+        return a
+    return up(a.numpy() if isinstance(a, torch.Tensor) else np.asarray(a), dev)
+
+
 class DeviceEventBatch:
     """An event batch resident in HBM (uint32/uint64 data held in int32/int64 tensors)."""
 
@@ -153,10 +169,8 @@ class DevicePathTable:
         return cls.from_arrays(latency_ns=lat, packet_loss=loss, device=device)
 
     def as_struct(self):
-        def ptr(t):
-            return t.data_ptr() if t is not None else None
-        return N.PathTableDev(self.n, 0, ptr(self.latency_ns), ptr(self.key), ptr(self.diag), self.unit,
-                              ptr(self.packet_loss))
+        return N.PathTableDev(self.n, 0, _ptr(self.latency_ns), _ptr(self.key), _ptr(self.diag), self.unit,
+                              _ptr(self.packet_loss))
 
 
 def send_packets_device(router, dbatch, table, out_status_t, out_deliver_t, out_order_t, out_host_off_t, counts_t=None,
@@ -255,26 +269,26 @@ def next_window(min_next_event_ns, runahead_ns, end_time_ns):
     return (int(ws.value), int(we.value)) if rc else None
 
 
-class EventQueues:
-    """The per-host packet-event queues, resident in HBM across rounds (srg_event_queues_*,
-    event_queue.hip.h).  The round loop: pop(window_end) -> the hosts run -> send() at the barrier
-    -> next_window(queues.min_next_event_ns, runahead, end_time).  Local events stay with the host."""
+class _Stage:
+    """A resident object of the native library behind a handle: created by one srg_*_create, destroyed
+    once by cls._destroy (the name of its srg_*_destroy), called with the handle in front."""
+    _destroy = None
+    _h = None
 
-    def __init__(self, router, num_hosts, reserve=0):
-        self.router, self.num_hosts = router, int(num_hosts)
+    def _create(self, fn, router, *args):
+        """fn(router handle, *args, &handle, err, len): sets router, dev and _h, or raises."""
+        self.router = router
         self.dev = torch.device(f"cuda:{router.device}")
         h = ctypes.c_void_p()
         err = ctypes.create_string_buffer(1024)
-        rc = N.lib().srg_event_queues_create(router._h, self.num_hosts, int(reserve), ctypes.byref(h), err, len(err))
+        rc = fn(router._h, *args, ctypes.byref(h), err, len(err))
         if rc != N.SRG_OK:
             _raise(rc, err.value.decode(errors="replace"))
         self._h = h
-        self.num_queued = 0
-        self.min_next_event_ns = 2**64 - 1
 
     def close(self):
         if self._h:
-            N.lib().srg_event_queues_destroy(self._h)
+            getattr(N.lib(), self._destroy)(self._h)
             self._h = None
 
     def __del__(self):
@@ -283,44 +297,56 @@ class EventQueues:
         except Exception:
             pass
 
+    def _call(self, fn, result_struct, *args, stream=None):
+        """A raw *_device call fn(handle, *args, stream, &result, err, len) -> (rc, result struct,
+        message); raises nothing."""
+        res = result_struct()
+        err = ctypes.create_string_buffer(1024)
+        s = stream if stream is not None else torch.cuda.current_stream(self.dev)
+        rc = fn(self._h, *args, ctypes.c_void_p(s.cuda_stream), ctypes.byref(res), err, len(err))
+        return rc, res, err.value.decode(errors="replace")
+
+
+class EventQueues(_Stage):
+    """The per-host packet-event queues, resident in HBM across rounds (srg_event_queues_*,
+    event_queue.hip.h).  The round loop: pop(window_end) -> the hosts run -> send() at the barrier
+    -> next_window(queues.min_next_event_ns, runahead, end_time).  Local events stay with the host."""
+
+    _destroy = "srg_event_queues_destroy"
+
+    def __init__(self, router, num_hosts, reserve=0):
+        self.num_hosts = int(num_hosts)
+        self._create(N.lib().srg_event_queues_create, router, self.num_hosts, int(reserve))
+        self.num_queued = 0
+        self.min_next_event_ns = 2**64 - 1
+
     def __len__(self):
         return self.num_queued
 
-    def _done(self, rc, res, err):
-        if rc != N.SRG_OK:
-            _raise_queue(rc, err.value.decode(errors="replace"))
-        self.num_queued, self.min_next_event_ns = int(res.num_queued), int(res.min_next_event_ns)
-        return res.as_dict()
+    def _moved(self, rc, res):
+        if rc == N.SRG_OK:
+            self.num_queued, self.min_next_event_ns = int(res.num_queued), int(res.min_next_event_ns)
 
     def push(self, dbatch, deliver_t, order_t, num_order, tags_t=None, stream=None):
         """dbatch: the DeviceEventBatch / DeviceSendBatch that order_packet_events_device /
         send_packets_device took; deliver_t, order_t: what it wrote; num_order: n / num_sent;
         tags_t: int64 [n] on the device (None: an event's tag is its index)."""
-        res = N.QueueResult()
-        err = ctypes.create_string_buffer(1024)
         b = dbatch.as_struct()
-        s = stream if stream is not None else torch.cuda.current_stream(self.dev)
-        rc = N.lib().srg_event_queues_push_device(
-            self._h, ctypes.byref(b), deliver_t.data_ptr(), order_t.data_ptr(), int(num_order),
-            tags_t.data_ptr() if tags_t is not None else None, ctypes.c_void_p(s.cuda_stream), ctypes.byref(res), err,
-            len(err))
-        return self._done(rc, res, err)
+        rc, res, msg = self._call(N.lib().srg_event_queues_push_device, N.QueueResult, ctypes.byref(b),
+                                  deliver_t.data_ptr(), order_t.data_ptr(), int(num_order), _ptr(tags_t), stream=stream)
+        if rc != N.SRG_OK:
+            _raise_queue(rc, msg)
+        self._moved(rc, res)
+        return res.as_dict()
 
     def pop_device(self, until_ns, capacity, out_time_t, out_src_t, out_id_t, out_tag_t, out_off_t, stream=None):
         """Raw call; returns (rc, result dict, message) and raises nothing: a short capacity is
         SRG_ERR_ARG with num_moved = the count needed."""
-        res = N.QueueResult()
-        err = ctypes.create_string_buffer(1024)
-        s = stream if stream is not None else torch.cuda.current_stream(self.dev)
-
-        def ptr(t):
-            return t.data_ptr() if t is not None else None
-        rc = N.lib().srg_event_queues_pop_device(
-            self._h, int(until_ns), int(capacity), ptr(out_time_t), ptr(out_src_t), ptr(out_id_t), ptr(out_tag_t),
-            ptr(out_off_t), ctypes.c_void_p(s.cuda_stream), ctypes.byref(res), err, len(err))
-        if rc == N.SRG_OK:
-            self.num_queued, self.min_next_event_ns = int(res.num_queued), int(res.min_next_event_ns)
-        return rc, res.as_dict(), err.value.decode(errors="replace")
+        rc, res, msg = self._call(N.lib().srg_event_queues_pop_device, N.QueueResult, int(until_ns), int(capacity),
+                                  _ptr(out_time_t), _ptr(out_src_t), _ptr(out_id_t), _ptr(out_tag_t), _ptr(out_off_t),
+                                  stream=stream)
+        self._moved(rc, res)
+        return rc, res.as_dict(), msg
 
     def pop(self, until_ns):
         """Pops every event with time < until_ns.  Returns host arrays (time u64, src_host u32,
@@ -359,38 +385,22 @@ class EventQueues:
         return sres, qres, status
 
 
-class Inbound:
+class Inbound(_Stage):
     """The hosts' inbound path, resident in HBM across steps (srg_inbound_*, inbound.hip.h): per host
     the router's CoDel queue (codel_queue.rs:125-319) and the inbound relay with its token bucket
     (relay/mod.rs:111-288, token_bucket.rs:68-157).  step() takes what EventQueues.pop returned, plus
     each packet's total size; the caller folds min_next_wake_ns into the minimum it hands to
     next_window: a pending forward task is a local event of its host."""
 
+    _destroy = "srg_inbound_destroy"
+
     def __init__(self, router, bw_down_bits, sim_start_ns, bootstrap_end_ns, reserve=0):
-        self.router = router
-        self.dev = torch.device(f"cuda:{router.device}")
         bw = np.ascontiguousarray(bw_down_bits, dtype=np.uint64)
         self.num_hosts = int(bw.shape[0])
-        h = ctypes.c_void_p()
-        err = ctypes.create_string_buffer(1024)
-        rc = N.lib().srg_inbound_create(router._h, self.num_hosts, bw.ctypes.data, int(sim_start_ns),
-                                        int(bootstrap_end_ns), int(reserve), ctypes.byref(h), err, len(err))
-        if rc != N.SRG_OK:
-            _raise(rc, err.value.decode(errors="replace"))
-        self._h = h
+        self._create(N.lib().srg_inbound_create, router, self.num_hosts, bw.ctypes.data, int(sim_start_ns),
+                     int(bootstrap_end_ns), int(reserve))
         self.num_queued = 0
         self.min_next_wake_ns = 2**64 - 1
-
-    def close(self):
-        if self._h:
-            N.lib().srg_inbound_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def step_device(self, until_ns, num_arrivals, time_t, size_t, tag_t, host_off_t, capacity, out_status_t, out_time_t,
                     out_tag_t, out_off_t, stream=None):
@@ -398,29 +408,20 @@ class Inbound:
         SRG_ERR_ARG with num_forwarded + num_dropped = the count needed.  time_t, tag_t, host_off_t
         int64 and size_t int32 tensors on the device, as EventQueues.pop_device wrote them;
         outputs uint8 / int64 / int64 [capacity] and int64 [num_hosts + 1]."""
-        res = N.InboundResult()
-        err = ctypes.create_string_buffer(1024)
-        s = stream if stream is not None else torch.cuda.current_stream(self.dev)
-
-        def ptr(t):
-            return t.data_ptr() if t is not None else None
-        rc = N.lib().srg_inbound_step_device(
-            self._h, int(until_ns), int(num_arrivals), ptr(time_t), ptr(size_t), ptr(tag_t), ptr(host_off_t),
-            int(capacity), ptr(out_status_t), ptr(out_time_t), ptr(out_tag_t), ptr(out_off_t),
-            ctypes.c_void_p(s.cuda_stream), ctypes.byref(res), err, len(err))
+        rc, res, msg = self._call(N.lib().srg_inbound_step_device, N.InboundResult, int(until_ns), int(num_arrivals),
+                                  _ptr(time_t), _ptr(size_t), _ptr(tag_t), _ptr(host_off_t), int(capacity),
+                                  _ptr(out_status_t), _ptr(out_time_t), _ptr(out_tag_t), _ptr(out_off_t), stream=stream)
         if rc == N.SRG_OK:
             self.num_queued, self.min_next_wake_ns = int(res.num_queued), int(res.min_next_wake_ns)
-        return rc, res.as_dict(), err.value.decode(errors="replace")
+        return rc, res.as_dict(), msg
 
     def step(self, until_ns, time, size, tag, host_offsets):
         """Device tensors (or host arrays, uploaded) in; returns device tensors (status uint8, time
         int64, tag int64, host_offsets int64 [H + 1], result).  Sized by num_queued + arrivals,
         which always suffices."""
         dev = self.dev
-
-        def dev_t(a, up):
-            return a if isinstance(a, torch.Tensor) else up(np.asarray(a), dev)
-        time_t, size_t, tag_t, off_t = dev_t(time, _i64), dev_t(size, _i32), dev_t(tag, _i64), dev_t(host_offsets, _i64)
+        time_t, size_t, tag_t = _dev_t(time, _i64, dev), _dev_t(size, _i32, dev), _dev_t(tag, _i64, dev)
+        off_t = _dev_t(host_offsets, _i64, dev)
         n = int(time_t.numel())
         cap = self.num_queued + n
         status = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
@@ -441,7 +442,7 @@ class Inbound:
         return out.as_dict()
 
 
-class Outbound:
+class Outbound(_Stage):
     """The hosts' outbound path, resident in HBM across steps (srg_outbound_*, outbound.hip.h): per
     host the sockets' control and data FIFOs, the interface's qdisc structure (the reference's socket
     heap restated literally, or the round-robin queue: network_interface.c:205-294,
@@ -451,36 +452,19 @@ class Outbound:
     the returned time as their send_time_ns.  The caller folds min_next_wake_ns into the minimum it
     hands to next_window: a pending forward task is a local event of its host."""
 
+    _destroy = "srg_outbound_destroy"
+
     def __init__(self, router, bw_up_bits, sockets_per_host, qdisc, sim_start_ns, bootstrap_end_ns, reserve=0):
-        self.router = router
-        self.dev = torch.device(f"cuda:{router.device}")
         bw = np.ascontiguousarray(bw_up_bits, dtype=np.uint64)
         ns = np.ascontiguousarray(sockets_per_host, dtype=np.uint32)
         if bw.shape != ns.shape:
             _raise(N.SRG_ERR_ARG, "bw_up_bits and sockets_per_host differ in length")
         self.num_hosts = int(bw.shape[0])
         self.sockets_per_host = ns
-        h = ctypes.c_void_p()
-        err = ctypes.create_string_buffer(1024)
-        rc = N.lib().srg_outbound_create(router._h, self.num_hosts, bw.ctypes.data, ns.ctypes.data, int(qdisc),
-                                         int(sim_start_ns), int(bootstrap_end_ns), int(reserve), ctypes.byref(h), err,
-                                         len(err))
-        if rc != N.SRG_OK:
-            _raise(rc, err.value.decode(errors="replace"))
-        self._h = h
+        self._create(N.lib().srg_outbound_create, router, self.num_hosts, bw.ctypes.data, ns.ctypes.data, int(qdisc),
+                     int(sim_start_ns), int(bootstrap_end_ns), int(reserve))
         self.num_queued = 0
         self.min_next_wake_ns = 2**64 - 1
-
-    def close(self):
-        if self._h:
-            N.lib().srg_outbound_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def step_device(self, until_ns, num_offers, time_t, socket_t, priority_t, size_t, flags_t, tag_t, host_off_t, capacity,
                     out_status_t, out_time_t, out_tag_t, out_off_t, stream=None):
@@ -488,33 +472,22 @@ class Outbound:
         SRG_ERR_ARG with num_sent + num_local = the count needed.  time_t, priority_t, tag_t,
         host_off_t int64, socket_t, size_t int32 and flags_t uint8 (or None) tensors on the device;
         outputs uint8 / int64 / int64 [capacity] and int64 [num_hosts + 1]."""
-        res = N.OutboundResult()
-        err = ctypes.create_string_buffer(1024)
-        s = stream if stream is not None else torch.cuda.current_stream(self.dev)
-
-        def ptr(t):
-            return t.data_ptr() if t is not None else None
-        rc = N.lib().srg_outbound_step_device(
-            self._h, int(until_ns), int(num_offers), ptr(time_t), ptr(socket_t), ptr(priority_t), ptr(size_t), ptr(flags_t),
-            ptr(tag_t), ptr(host_off_t), int(capacity), ptr(out_status_t), ptr(out_time_t), ptr(out_tag_t), ptr(out_off_t),
-            ctypes.c_void_p(s.cuda_stream), ctypes.byref(res), err, len(err))
+        rc, res, msg = self._call(N.lib().srg_outbound_step_device, N.OutboundResult, int(until_ns), int(num_offers),
+                                  _ptr(time_t), _ptr(socket_t), _ptr(priority_t), _ptr(size_t), _ptr(flags_t), _ptr(tag_t),
+                                  _ptr(host_off_t), int(capacity), _ptr(out_status_t), _ptr(out_time_t), _ptr(out_tag_t),
+                                  _ptr(out_off_t), stream=stream)
         if rc == N.SRG_OK:
             self.num_queued, self.min_next_wake_ns = int(res.num_queued), int(res.min_next_wake_ns)
-        return rc, res.as_dict(), err.value.decode(errors="replace")
+        return rc, res.as_dict(), msg
 
     def step(self, until_ns, time, socket, priority, size, flags, tag, host_offsets):
         """Device tensors (or host arrays, uploaded) in; returns device tensors (status uint8, time
         int64, tag int64, host_offsets int64 [H + 1], result).  Sized by num_queued + offers, which
         always suffices."""
         dev = self.dev
-
-        def dev_t(a, up):
-            return a if isinstance(a, torch.Tensor) or a is None else up(np.asarray(a), dev)
-
-        def _u8(a, d):
-            return torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint8)).to(d)
-        time_t, sock_t, prio_t, size_t = dev_t(time, _i64), dev_t(socket, _i32), dev_t(priority, _i64), dev_t(size, _i32)
-        flags_t, tag_t, off_t = dev_t(flags, _u8), dev_t(tag, _i64), dev_t(host_offsets, _i64)
+        time_t, sock_t, prio_t = _dev_t(time, _i64, dev), _dev_t(socket, _i32, dev), _dev_t(priority, _i64, dev)
+        size_t, flags_t = _dev_t(size, _i32, dev), _dev_t(flags, _u8, dev)
+        tag_t, off_t = _dev_t(tag, _i64, dev), _dev_t(host_offsets, _i64, dev)
         n = int(time_t.numel())
         cap = max(self.num_queued + n, 1)
         status = torch.empty(cap, dtype=torch.uint8, device=dev)
@@ -548,7 +521,7 @@ class Outbound:
         return [int(buf[i]) for i in range(int(n.value))]
 
 
-class SocketsIn:
+class SocketsIn(_Stage):
     """Interface receive, resident in HBM across steps (srg_sockets_in_*, sockets_in.hip.h): what the
     inbound relay's dst.push(packet) does (relay/mod.rs:261-271) -- the interface's socket lookup
     (network_interface.c:140-202), the UDP sockets' receive buffers (udp.rs:108-168, 1081-1157) and the
@@ -556,32 +529,15 @@ class SocketsIn:
     (udp.rs:497-546).  step_device() takes the arrays Inbound.step_device / Round.receive_device wrote
     (deliver_status 1) or Round.send_device wrote (deliver_status SRG_ROUND_LOCAL) untouched."""
 
+    _destroy = "srg_sockets_in_destroy"
+
     def __init__(self, router, sockets_per_host, reserve=0):
-        self.router = router
-        self.dev = torch.device(f"cuda:{router.device}")
         ns = np.ascontiguousarray(sockets_per_host, dtype=np.uint32)
         self.num_hosts = int(ns.shape[0])
         self.sockets_per_host = ns
         self._packets = None
-        h = ctypes.c_void_p()
-        err = ctypes.create_string_buffer(1024)
-        rc = N.lib().srg_sockets_in_create(router._h, self.num_hosts, ns.ctypes.data, int(reserve), ctypes.byref(h), err,
-                                           len(err))
-        if rc != N.SRG_OK:
-            _raise(rc, err.value.decode(errors="replace"))
-        self._h = h
+        self._create(N.lib().srg_sockets_in_create, router, self.num_hosts, ns.ctypes.data, int(reserve))
         self.num_buffered_messages = 0
-
-    def close(self):
-        if self._h:
-            N.lib().srg_sockets_in_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def set_packets(self, protocol_t, src_ip_t, src_port_t, dst_port_t, total_size_t, payload_size_t):
         """The packet table by tag, borrowed: uint8, int32 (u32 data), int16 (u16), int16, int32, int32
@@ -624,20 +580,13 @@ class SocketsIn:
                     r_host_off, out_status, out_slot, out_r_status, out_r_tag, out_r_time, out_r_payload, stream=None):
         """Raw call; returns (rc, result dict, message) and raises nothing.  Every array is a device
         tensor, a raw device pointer (int, e.g. a borrowed pointer of a Round result) or None."""
-        res = N.SocketsInResult()
-        err = ctypes.create_string_buffer(1024)
-        s = stream if stream is not None else torch.cuda.current_stream(self.dev)
-
-        def ptr(t):
-            return t.data_ptr() if isinstance(t, torch.Tensor) else (int(t) if t else None)
-        rc = N.lib().srg_sockets_in_step_device(
-            self._h, int(num_rows), ptr(status), ptr(time), ptr(tag), ptr(host_off), int(deliver_status), int(num_reads),
-            ptr(r_time), ptr(r_slot), ptr(r_flags), ptr(r_host_off), ptr(out_status), ptr(out_slot), ptr(out_r_status),
-            ptr(out_r_tag), ptr(out_r_time), ptr(out_r_payload), ctypes.c_void_p(s.cuda_stream), ctypes.byref(res), err,
-            len(err))
+        rc, res, msg = self._call(N.lib().srg_sockets_in_step_device, N.SocketsInResult, int(num_rows), _ptr(status),
+                                  _ptr(time), _ptr(tag), _ptr(host_off), int(deliver_status), int(num_reads), _ptr(r_time),
+                                  _ptr(r_slot), _ptr(r_flags), _ptr(r_host_off), _ptr(out_status), _ptr(out_slot),
+                                  _ptr(out_r_status), _ptr(out_r_tag), _ptr(out_r_time), _ptr(out_r_payload), stream=stream)
         if rc == N.SRG_OK:
             self.num_buffered_messages = int(res.num_buffered_messages)
-        return rc, res.as_dict(), err.value.decode(errors="replace")
+        return rc, res.as_dict(), msg
 
     def step(self, status, time, tag, host_offsets, deliver_status=1, r_time=None, r_slot=None, r_flags=None,
              r_host_offsets=None):
@@ -645,9 +594,6 @@ class SocketsIn:
         (out_status u8, out_slot u32, read_status u8, read_tag u64, read_time u64, read_payload u32,
         result)."""
         dev = self.dev
-
-        def u8(a):
-            return None if a is None else torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint8)).to(dev)
         n = int(len(time))
         nr = 0 if r_time is None else int(len(r_time))
         time_t, tag_t, off_t = _i64(time, dev), _i64(tag, dev), _i64(host_offsets, dev)
@@ -660,8 +606,9 @@ class SocketsIn:
         q_tag = torch.empty(max(nr, 1), dtype=torch.int64, device=dev)
         q_time = torch.empty(max(nr, 1), dtype=torch.int64, device=dev)
         q_pay = torch.empty(max(nr, 1), dtype=torch.int32, device=dev)
-        rc, res, msg = self.step_device(n, u8(status), time_t, tag_t, off_t, deliver_status, nr, rt_t, rs_t,
-                                        u8(r_flags) if nr else None, ro_t, o_st, o_sl, q_st, q_tag, q_time, q_pay)
+        rc, res, msg = self.step_device(n, _dev_t(status, _u8, dev), time_t, tag_t, off_t, deliver_status, nr, rt_t, rs_t,
+                                        _dev_t(r_flags, _u8, dev) if nr else None, ro_t, o_st, o_sl, q_st, q_tag, q_time,
+                                        q_pay)
         if rc != N.SRG_OK:
             _raise_queue(rc, msg)
         return (o_st[:n].cpu().numpy(), o_sl[:n].cpu().numpy().view(np.uint32), q_st[:nr].cpu().numpy(),
@@ -712,18 +659,17 @@ class _PartView:
         return self._base.host_order(self, h)
 
 
-class Round:
+class Round(_Stage):
     """A round on the device (srg_round_*, round.hip.h): the event queues, the inbound and the outbound
     path, each host's Xoshiro256++ generator (host.rs:233) and event-id counter (host.rs:690) and the
     hosts' nodes in HBM, over the caller's packet table indexed by tag.  A round is
     receive(window_end) -> the hosts run -> send(window_end, offers) -> next_window(result
     ["next_start_ns"], ...).  An error leaves everything as it was.  The part views give host_state /
     host_order of the round's own parts; stepping a part is not possible through them."""
+    _destroy = "srg_round_destroy"
 
     def __init__(self, router, host_node, table, bw_up_bits, bw_down_bits, sockets_per_host, qdisc, node_seed,
                  sim_start_ns, bootstrap_end_ns, sim_end_ns, reserve=0):
-        self.router = router
-        self.dev = torch.device(f"cuda:{router.device}")
         hn = np.ascontiguousarray(host_node, dtype=np.uint32)
         up = np.ascontiguousarray(bw_up_bits, dtype=np.uint64)
         down = np.ascontiguousarray(bw_down_bits, dtype=np.uint64)
@@ -736,29 +682,14 @@ class Round:
         self.table = table  # (keeps the borrowed device arrays alive)
         self._packets = None
         t = table.as_struct()
-        h = ctypes.c_void_p()
-        err = ctypes.create_string_buffer(1024)
-        rc = N.lib().srg_round_create(router._h, self.num_hosts, hn.ctypes.data, ctypes.byref(t), up.ctypes.data,
-                                      down.ctypes.data, ns.ctypes.data, int(qdisc), seed.ctypes.data, int(sim_start_ns),
-                                      int(bootstrap_end_ns), int(sim_end_ns), int(reserve), ctypes.byref(h), err, len(err))
-        if rc != N.SRG_OK:
-            _raise(rc, err.value.decode(errors="replace"))
-        self._h = h
         L = N.lib()
+        self._create(L.srg_round_create, router, self.num_hosts, hn.ctypes.data, ctypes.byref(t), up.ctypes.data,
+                     down.ctypes.data, ns.ctypes.data, int(qdisc), seed.ctypes.data, int(sim_start_ns),
+                     int(bootstrap_end_ns), int(sim_end_ns), int(reserve))
+        h = self._h
         self.queues = _PartView(ctypes.c_void_p(L.srg_round_queues(h)), EventQueues, self)
         self.inbound = _PartView(ctypes.c_void_p(L.srg_round_inbound(h)), Inbound, self)
         self.outbound = _PartView(ctypes.c_void_p(L.srg_round_outbound(h)), Outbound, self)
-
-    def close(self):
-        if self._h:
-            N.lib().srg_round_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def set_packets(self, dst_host_t, total_size_t, payload_size_t):
         """int32 tensors [num_packets] on the device (u32 data), indexed by tag; borrowed."""
@@ -773,12 +704,7 @@ class Round:
 
     def receive_device(self, until_ns, stream=None):
         """Raw call; returns (rc, RoundReceiveResult, message) and raises nothing."""
-        res = N.RoundReceiveResult()
-        err = ctypes.create_string_buffer(1024)
-        s = stream if stream is not None else torch.cuda.current_stream(self.dev)
-        rc = N.lib().srg_round_receive_device(self._h, int(until_ns), ctypes.c_void_p(s.cuda_stream), ctypes.byref(res),
-                                              err, len(err))
-        return rc, res, err.value.decode(errors="replace")
+        return self._call(N.lib().srg_round_receive_device, N.RoundReceiveResult, int(until_ns), stream=stream)
 
     def receive(self, until_ns):
         """pop(until) -> sizes -> inbound step.  Returns a dict: the result fields, the popped events
@@ -801,30 +727,17 @@ class Round:
                     stream=None):
         """Raw call; returns (rc, RoundSendResult, message) and raises nothing.  time_t, priority_t,
         tag_t, host_off_t int64, socket_t int32, flags_t uint8 (or None) tensors on the device."""
-        res = N.RoundSendResult()
-        err = ctypes.create_string_buffer(1024)
-        s = stream if stream is not None else torch.cuda.current_stream(self.dev)
-
-        def ptr(t):
-            return t.data_ptr() if t is not None else None
-        rc = N.lib().srg_round_send_device(
-            self._h, int(until_ns), int(num_offers), ptr(time_t), ptr(socket_t), ptr(priority_t), ptr(flags_t), ptr(tag_t),
-            ptr(host_off_t), ptr(counts_t), ctypes.c_void_p(s.cuda_stream), ctypes.byref(res), err, len(err))
-        return rc, res, err.value.decode(errors="replace")
+        return self._call(N.lib().srg_round_send_device, N.RoundSendResult, int(until_ns), int(num_offers), _ptr(time_t),
+                          _ptr(socket_t), _ptr(priority_t), _ptr(flags_t), _ptr(tag_t), _ptr(host_off_t), _ptr(counts_t),
+                          stream=stream)
 
     def send(self, until_ns, time, socket, priority, flags, tag, host_offsets, counts=None):
         """offers -> outbound step -> draw -> send -> push.  Device tensors (or host arrays, uploaded)
         in.  Returns a dict: the result fields and, per leaving packet grouped by host in leaving
         order, status (uint8, SRG_ROUND_*), time, tag and host_offsets as owned device tensors."""
         dev = self.dev
-
-        def dev_t(a, up):
-            return a if isinstance(a, torch.Tensor) or a is None else up(np.asarray(a), dev)
-
-        def _u8(a, d):
-            return torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint8)).to(d)
-        time_t, sock_t, prio_t = dev_t(time, _i64), dev_t(socket, _i32), dev_t(priority, _i64)
-        flags_t, tag_t, off_t = dev_t(flags, _u8), dev_t(tag, _i64), dev_t(host_offsets, _i64)
+        time_t, sock_t, prio_t = _dev_t(time, _i64, dev), _dev_t(socket, _i32, dev), _dev_t(priority, _i64, dev)
+        flags_t, tag_t, off_t = _dev_t(flags, _u8, dev), _dev_t(tag, _i64, dev), _dev_t(host_offsets, _i64, dev)
         rc, res, msg = self.send_device(until_ns, int(time_t.numel()), time_t, sock_t, prio_t, flags_t, tag_t, off_t, counts)
         if rc != N.SRG_OK:
             _raise_queue(rc, msg)
